@@ -10,6 +10,14 @@ hipBLASLt, then the fused HIP view-synthesis loss) + backward + Adam, on one syn
 Workload = BASELINE.json configs[1]: KITTI shape 192x640, litemono, batch 12 per GPU, fp32, phase fine_tune (all
 networks optimised, every loss term active -- 20 of the schedule's 27 epochs).  Weak scaling: every rank processes its
 own batch; the only collective is DDP's gradient all-reduce over RCCL/xGMI.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, `config`).  --full adds what takes measurements of its own: the roofline figures of the photometric tile kernel
+and the loss path (HIP events around host-issued evaluations behind the timed region), the 3x3 convolution's roofline, and the
+bounded CPU baseline (unless --no_cpu_baseline).  --dump-outputs DIR writes what the last timed step returned -- the network
+outputs and the loss terms -- as DIR/<name>.npy (float32; a fixed sample of every tensor when all of them would exceed 64 MB).
+Every step runs with a step size of zero (see main()): each starts from the seeded initial weights, whatever rounding the
+library's reductions took in the steps before it.
 """
 import argparse
 import json
@@ -330,6 +338,41 @@ def pmc_traffic(a, opt, motion):
         return {"traffic": None}
 
 
+DUMP_LIMIT_BYTES = 60 << 20           # what --dump-outputs may write in all (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(directory, outputs, losses):
+    """--dump-outputs: every tensor of the step's (outputs, losses) as <directory>/<name>.npy, in float32 (float64 stays float64),
+    in the tensor's logical (N, C, H, W) order.  When all of them together exceed DUMP_LIMIT_BYTES, a tensor larger than an equal
+    share of the limit is replaced by a fixed sample of that many elements of its flattened values (sorted indices drawn from a
+    generator seeded by the file name: the same elements in every run of the same shapes)."""
+    import re
+    import zlib
+    import numpy as np
+    arrays = {}
+    for prefix, d in (("outputs", outputs), ("losses", losses)):
+        for k, v in d.items():
+            if not torch.is_tensor(v):
+                continue
+            name = prefix + "." + "_".join(str(x) for x in (k if isinstance(k, tuple) else (k,)))
+            name = re.sub(r"[^A-Za-z0-9_.+-]", "-", name)
+            t = v.detach()
+            arrays[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+    os.makedirs(directory, exist_ok=True)
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    share = DUMP_LIMIT_BYTES // (8 * max(len(arrays), 1))       # elements per tensor, float64 at worst
+    sampled = 0
+    for name, t in sorted(arrays.items()):
+        a = t.cpu().contiguous().numpy()
+        if total > DUMP_LIMIT_BYTES and a.size > share:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+            sampled += 1
+        np.save(os.path.join(directory, name + ".npy"), a)
+    note("--dump-outputs: {} arrays ({:.1f} MB before sampling, {} of them sampled to {} elements) -> {}".format(
+        len(arrays), total / 1e6, sampled, share, directory))
+
+
 def main():
     if os.environ.get("DD_FAULT_AFTER"):            # debugging aid: dump every thread's Python stack after N seconds (a hung run)
         import faulthandler
@@ -360,7 +403,14 @@ def main():
     ap.add_argument("--no_fused_loss", action="store_true", help="ablation: operator-by-operator loss path")
     ap.add_argument("--stats_only_side_frames", action="store_true",
                     help="NOT the headline: frames -1/+1 through the depth encoder only (same weights, statistics and losses; the reference also decodes them)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take measurements of their own: roofline of the tile kernel and the loss path, roofline of the "
+                         "3x3 convolution, CPU baseline (see --no_cpu_baseline); a plain run times the steps and prints the headline alone")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write the network outputs and loss terms of the last timed step to DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -412,6 +462,11 @@ def main():
         opt_args += ["--matmul_precision", a.matmul_precision]
     opt = DynamoOptions().parse(args=opt_args)
     opt.print_opt = False
+    # Every step is the whole training step -- forward, backward, Adam update -- with a step size of zero, so that every step starts
+    # from the seeded initial weights and two runs with the same arguments compute the same outputs.  (With a moving trajectory they
+    # cannot: the library's split-K weight gradients add with float atomics, in a different order from run to run, and forty steps of
+    # Adam from a random initialisation amplify that rounding to 10 % in the network outputs.)  The update's arithmetic is unchanged.
+    opt.learning_rate = 0.0
     opt.local_world_size, opt.ddp = world, dist_on
     opt.local_rank = local_rank
     opt.cuda_ids = [0] * max(world, 1) if share_device else list(range(max(world, 1)))
@@ -435,9 +490,10 @@ def main():
         return tr.train_step(dict(batch))            # a fresh dict without the pyramid keys: every step builds the target pyramid
 
     note("trainer built; warm-up (first step compiles / selects the MIOpen kernels)")
-    FL.PROFILE_EVENTS = []
+    FL.PROFILE_EVENTS = [] if a.full else None       # (--full: HIP events around the loss path of every host-issued step)
     hip = HL.load()
-    HL.check(hip.dd_photo_timing(1), "dd_photo_timing")          # HIP events around photo_tile_kernel alone, inside the library
+    if a.full:
+        HL.check(hip.dd_photo_timing(1), "dd_photo_timing")      # HIP events around photo_tile_kernel alone, inside the library
     mode = "eager" if a.no_fused_loss and a.mode != "graph" else a.mode
     capture_fallback = None              # auto mode: why the replayed step was not available, if it was not
     if mode == "auto":
@@ -490,10 +546,11 @@ def main():
         for _ in range(a.warmup):
             one_step()
     torch.cuda.synchronize()
-    warm_events = FL.PROFILE_EVENTS
-    FL.PROFILE_EVENTS = [] if mode == "eager" else None
+    warm_events = FL.PROFILE_EVENTS or []
+    FL.PROFILE_EVENTS = [] if mode == "eager" and a.full else None
     tile_us, tile_n = C.c_float(0), C.c_int(0)
-    HL.check(hip.dd_photo_timing_read(C.byref(tile_us), C.byref(tile_n), 1), "dd_photo_timing_read")   # eager warm-up launches
+    if a.full:
+        HL.check(hip.dd_photo_timing_read(C.byref(tile_us), C.byref(tile_n), 1), "dd_photo_timing_read")   # eager warm-up launches
     # (the timer stays on in both modes: the replayed step launches the tile kernel from the host between two graphs)
     if dist_on:
         dist.barrier()
@@ -511,7 +568,7 @@ def main():
         note("gradient all-reduce placement: {} (probe, ms/step, max over ranks: {})".format(seg_step.reduce_mode_chosen, seg_step.reduce_probe_ms))
         if dist_on:
             dist.barrier()
-    if seg_step is not None:
+    if seg_step is not None and a.full:
         seg_step.loss_events = []            # an event pair around the loss graph of every timed step (no host sync)
     note("warm-up done; timing {} steps".format(a.steps))
     if seg_step is not None:
@@ -541,6 +598,8 @@ def main():
         dist.all_gather(every, mine)
         enqueue_per_rank = [round(float(x), 3) for x in every]
     loss_val = float(losses["loss"].detach())
+    if a.dump_outputs and rank == 0:         # before anything else runs: a replayed step's outputs live in the graphs' static buffers
+        dump_outputs(a.dump_outputs, outputs, losses)
     if seg_step is not None and seg_step.timing:             # DD_SEG_TIMING=1: where the graphs of the last step sat on the GPU
         rows = []
         for _ in range(5):
@@ -580,7 +639,7 @@ def main():
                 "photo_us": statistics.median(e[0].elapsed_time(e[1]) for e in ev) * 1e3,
                 "path_us": statistics.median(e[0].elapsed_time(e[3]) for e in ev) * 1e3}
 
-    if seg_step is not None and not tr.time_tile_kernel:
+    if a.full and seg_step is not None and not tr.time_tile_kernel:
         # Roofline leg of the replayed step: inside a graph the tile kernel cannot be bracketed by events, so the loss path is evaluated
         # again directly behind the timed region, host-issued and alone on the stream, same kernels, same process, same batch of frames:
         #   "synthetic": on SURVEY.md 8(d)'s synthetic network outputs (low-frequency fields) -- what `roofline.frac` is quoted on;
@@ -598,10 +657,10 @@ def main():
     path_ms = [ev[0].elapsed_time(ev[3]) for ev in events if ev[2]]       # photometric + regularisers + assembly, launch to launch
     timed_in = "timed region" if mode == "eager" else "eager warm-up steps"
     replay_note = {}
-    if mode == "eager":
+    if a.full and mode == "eager":
         HL.check(hip.dd_photo_timing_read(C.byref(tile_us), C.byref(tile_n), 0), "dd_photo_timing_read")   # the timed region's launches
         HL.check(hip.dd_photo_timing(0), "dd_photo_timing")
-    elif seg_step is not None:
+    elif a.full and seg_step is not None:
         # The replayed step: every timed step recorded an event pair around its loss graph (stream time inside the step, beside the
         # other streams' kernels); the kernel times come from the host-issued evaluations behind the timed region (or, with
         # DD_BENCH_SPLIT_LOSS=1, from the tile kernel launched by the host between two graphs of the loss inside the timed region).
@@ -663,7 +722,7 @@ def main():
             "config": {"workload": "{} {} {}x{} batch={}/GPU phase={} (all loss terms of the phase), random-init weights".format(
                 a.dataset, a.depth_model, opt.height, opt.width, a.batch, a.phase),
                 "global_batch": a.batch * world, "parallelism": "dp{}".format(world), "mode": mode, "mode_requested": a.mode, "auto_probe": auto_note, "miopen_find": bool(opt.miopen_find), "channels_last": bool(a.channels_last),
-                "loss_path": "operators" if a.no_fused_loss else "fused HIP", "final_loss": round(loss_val, 6),
+                "loss_path": "operators" if a.no_fused_loss else "fused HIP", "final_loss": round(loss_val, 6), "learning_rate": opt.learning_rate,
                 "distinct_hw_queues_found": _queues_found(), "rccl_ranks": dist.get_world_size() if dist_on else 0, "dist_backend": backend if dist_on else None, "capture_fallback": capture_fallback,
                 "reduce_mode": (getattr(seg_step, "reduce_mode_chosen", None) if seg_step is not None else ("flat buffer, one all-reduce behind backward()" if dist_on else None)),
                 "reduce_probe_ms": getattr(seg_step, "reduce_probe_ms", None) if seg_step is not None else None,
@@ -686,10 +745,11 @@ def main():
                 "optimizer_update": ("dd_adam_multi (one launch)" if getattr(seg_step, "one_launch_adam", None) is not None else "torch multi-tensor Adam ({})".format(getattr(seg_step, "adam_fallback", None))) if seg_step is not None else "torch multi-tensor Adam (eager step)",
                 "side_frames": "depth encoder only (--stats_only_side_frames, NOT the headline)" if a.stats_only_side_frames else "full depth net, as the reference",
                 "host_enqueue_ms_per_step": round(t_enqueued / a.steps * 1e3, 3), "host_enqueue_ms_per_rank": enqueue_per_rank},
-            "roofline": roof,
-            "roofline_conv3x3": _conv_mfma_roofline() if _mfma_conv_calls() > 0 else None,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            line["roofline"] = roof
+            line["roofline_conv3x3"] = _conv_mfma_roofline() if _mfma_conv_calls() > 0 else None
+        if a.full and world == 1 and not a.no_cpu_baseline:
             note("timed region done; running the CPU baseline (bounded sample)")
             line["cpu_baseline"] = cpu_baseline_guarded([x for x in opt_args if x not in ("--no_hip_graph", "--nchw", "--single_stream", "--no_miopen_find", "--miopen_find")], a.phase, sample_batch=2)
             # the unmodified reference itself cannot travel to the GPU box; its timing in the build container is on record

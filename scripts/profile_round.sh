@@ -11,7 +11,7 @@ root=$PWD
 out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python $root/bench.py --no_cpu_baseline ${DD_BENCH_ARGS:-} > $out/bench.log 2>&1 )
+( cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python $root/bench.py --full --no_cpu_baseline ${DD_BENCH_ARGS:-} > $out/bench.log 2>&1 )
 grep "^{" $out/bench.log | tail -1 > $out/${tag}_bench_line.json
 st=$(find $out/bench -name '*kernel_stats.csv' | head -1)
 tr=$(find $out/bench -name '*kernel_trace.csv' | head -1)

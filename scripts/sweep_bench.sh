@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/.." || exit 1
 row() {  # label, args...
   label=$1; shift
-  timeout 420 python bench.py --no_cpu_baseline "$@" 2>/dev/null | grep "^{" | tail -1 | python -c "
+  timeout 420 python bench.py --full --no_cpu_baseline "$@" 2>/dev/null | grep "^{" | tail -1 | python -c "
 import json,sys
 t=sys.stdin.read()
 if not t.strip():

@@ -21,7 +21,7 @@ def last_json_line(text):
 
 def test_single_gpu_line_carries_the_roofline_of_the_replayed_step():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "graph"] + SMALL, env=env, stdout=subprocess.PIPE,
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "graph", "--full"] + SMALL, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     line = last_json_line(res.stdout)
@@ -48,7 +48,7 @@ def test_single_gpu_line_carries_the_roofline_of_the_replayed_step():
 def test_single_gpu_line_with_the_instrumented_split_loss():
     """DD_BENCH_SPLIT_LOSS=1 (round 3's instrumented step): graph | tile kernel launched by the host | graph, timed inside the timed region."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", DD_BENCH_SPLIT_LOSS="1")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "graph"] + SMALL, env=env, stdout=subprocess.PIPE,
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "graph", "--full"] + SMALL, env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     roof = last_json_line(res.stdout)["roofline"]
@@ -86,3 +86,25 @@ def test_two_rank_bench_path_on_one_gpu():
     assert line["config"]["mode"] in ("graph", "eager") and line["config"]["auto_probe"] is not None
     assert line["value"] > 0 and line["config"]["final_loss"] == line["config"]["final_loss"]          # finite
     assert sum(1 for ln in res.stdout.splitlines() if ln.startswith("{")) == 1                         # rank 0 alone prints the line
+
+
+def test_plain_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline and none of the figures --full measures; --dump-outputs writes what the last
+    timed step returned (network outputs, loss terms) as float32 / float64 .npy files within 64 MB."""
+    import numpy as np
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    dump = tmp_path / "dump"
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "graph", "--dump-outputs", str(dump)] + SMALL, env=env,
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert res.returncode == 0, res.stderr[-4000:]
+    line = last_json_line(res.stdout)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert key in line, key
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["config"]["mode"] == "graph"
+    assert "roofline" not in line and "roofline_conv3x3" not in line and "cpu_baseline" not in line, sorted(line)
+    files = sorted(dump.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    arrays = {f.name[:-4]: np.load(f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert "outputs.disp_0_0" in arrays and np.isfinite(arrays["outputs.disp_0_0"]).all()
+    assert abs(float(arrays["losses.loss"]) - line["config"]["final_loss"]) <= 1e-6 + 1e-6 * abs(line["config"]["final_loss"])
