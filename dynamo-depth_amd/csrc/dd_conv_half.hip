@@ -12,17 +12,20 @@
 // Implicit GEMM, M = output pixels, N = output channels, K = 9 taps x input channels, laid out for ONE product per operand pair:
 //   * a workgroup (256 threads, 4 waves) owns 8 rows x 32 columns of output pixels of one image and 32*NB output channels (NB <= 2);
 //     wave w owns tile rows 2w, 2w+1 and all NB channel blocks: 2*NB accumulators of 32 x 32;
-//   * K advances in chunks of 32 input channels (two K-16 MFMA steps per tap).  A chunk's input halo (10 x 34 pixels x 32 channels,
-//     80-byte pixel stride: every A fragment is one conflict-free ds_read_b128 at a constant offset) AND all of the chunk's weight
-//     fragments (9 taps x 2 steps x NB KB, fragment order, packed once per step from the fp32 master weights by
-//     conv_half_pack_kernel: the cast that autocast would launch per layer happens there) are staged together: TWO LDS barriers per
-//     chunk of 36*NB MFMAs per wave, none inside it -- the fp32 kernel's barrier per tap would cost as much as the four MFMAs
-//     between two of them here;
+//   * K advances in chunks of 16 input channels (one K-16 MFMA step per tap).  A chunk's input halo (10 x 34 pixels x 16 channels,
+//     48-byte pixel stride: every A fragment is one conflict-free ds_read_b128 at a constant offset) AND all of the chunk's weight
+//     fragments (9 taps x NB KB, fragment order, packed once per step from the fp32 master weights by conv_half_pack_kernel: the
+//     cast that autocast would launch per layer happens there) are staged together: TWO LDS barriers per chunk of 18*NB MFMAs per
+//     wave, none inside it -- the fp32 kernel's barrier per tap would cost as much as the four MFMAs between two of them here;
 //   * the next chunk's halo and weights are fetched into registers under the current chunk's MFMAs (plain loads with counted waits;
 //     LDS-only barriers keep them in flight);
-//   * 27 KB of halo + 18*NB KB of weights (64 KB at NB = 2): two workgroups per CU, one staging while the other multiplies.
+//   * 16 KB of halo + 9*NB KB of weights (34 KB at NB = 2), registers inside the launch bound: THREE workgroups per CU.  Every
+//     workgroup waits for its first halo, so occupancy is what pays: 32-channel chunks (64 KB, two workgroups per CU) lost to the
+//     library, four workgroups (128 VGPRs, spills) and a halo prefetch two chunks deep lost to this layout
+//     (profiles/r06_conv_half_variants.txt).
 // The data gradient is the same kernel on the output gradient with the weights packed transposed and mirrored (pad' = 2 - pad).
-// The weight gradient of these layers stays with the library's half-precision kernel (hipops/functions.py: HalfConvFn).
+// The weight gradient is conv_half_wgrad_kernel below: fp32 result, one partial per workgroup, fixed-order fold (hipops/functions.py:
+// HalfConvFn runs all three; below 32 channels on either side its weight gradient stays with the library).
 #include <hip/hip_runtime.h>
 
 #include "../../include/dynamo_hip.h"
@@ -41,24 +44,18 @@ typedef __attribute__((ext_vector_type(4))) unsigned u4;        // native vector
 
 constexpr int TH = 8, TW = 32, NT = 256;
 constexpr int HH = TH + 2, HW = TW + 2, HN = HH * HW;      // halo: 340 pixels
-#ifndef DD_CH_KS
-#define DD_CH_KS 1
-#endif
-constexpr int KS = DD_CH_KS;                                // K-16 MFMA steps per tap and chunk
-constexpr int CK = 16 * KS;                                 // input channels per chunk
-constexpr int PSTR = 32 * KS + 16;                          // bytes per halo pixel: the chunk's halves + 16 bytes of padding (80 = 5 x 16, 48 = 3 x 16: conflict-free)
-constexpr int A_BYTES = HN * PSTR;                          // 27 200 (KS = 2)
+constexpr int CK = 16;                                      // input channels per chunk = the K of one MFMA
+constexpr int PSTR = 48;                                    // bytes per halo pixel: the chunk's two halves + 16 bytes of padding (3 x 16: conflict-free)
+constexpr int A_BYTES = HN * PSTR;                          // 16 320
 constexpr int FRAG = 1024;                                  // one B fragment: 64 lanes x 16 bytes
-constexpr int OCT = 2 * KS;                                 // channel octets (16-byte items) per pixel and chunk
+constexpr int OCT = 2;                                      // channel octets (16-byte items) per pixel and chunk
 constexpr int A_ITEMS = HN * OCT;                           // 16-byte items of a chunk's halo (pixel, channel octet)
 constexpr int A_PRE = (A_ITEMS + NT - 1) / NT;              // 6 per thread (the last round is partial)
-#ifndef DD_CH_MINWG
-#define DD_CH_MINWG 3
-#endif
+constexpr int MINWG = 3;                                    // workgroups per CU the launch bound asks for (<= 168 VGPRs)
 
 __host__ __device__ inline int blocks_for(int n_out) { return n_out <= 32 ? 1 : 2; }
 template <int NB>
-constexpr int b_bytes() { return 9 * KS * NB * FRAG; }      // a chunk's weight fragments: [tap][K step][n block][lane] x 16 bytes
+constexpr int b_bytes() { return 9 * NB * FRAG; }           // a chunk's weight fragments: [tap][n block][lane] x 16 bytes
 template <int NB>
 constexpr int b_pre() { return (b_bytes<NB>() / 16 + NT - 1) / NT; }
 template <int NB>
@@ -74,8 +71,8 @@ __device__ __forceinline__ unsigned short pack1(float a) {
   return static_cast<unsigned short>(pack2<F16>(a, 0.f) & 0xffffu);
 }
 
-// pack layout: [n tile][chunk][tap][K step][n block in tile][lane] x 16 bytes.  Lane l of a fragment holds, for output channel
-// (tile * NB + block) * 32 + (l & 31), the input channels chunk * 32 + step * 16 + (l >> 5) * 8 + 0..7 of the tap, converted from the fp32
+// pack layout: [n tile][chunk][tap][n block in tile][lane] x 16 bytes.  Lane l of a fragment holds, for output channel
+// (tile * NB + block) * 32 + (l & 31), the input channels chunk * 16 + (l >> 5) * 8 + 0..7 of the tap, converted from the fp32
 // weights.  transposed = 0: out = cout, in = cin, tap as stored (forward).  transposed = 1: out = cin, in = cout, tap mirrored (data gradient).
 template <bool F16>
 __global__ __launch_bounds__(256) void conv_half_pack_kernel(const float* __restrict__ w, long long s_co, long long s_ci, long long s_kh, long long s_kw,
@@ -89,9 +86,9 @@ __global__ __launch_bounds__(256) void conv_half_pack_kernel(const float* __rest
   if (bwd ? (f >= frags_bwd || !pack_bwd) : !pack_fwd) return;
   const int n_out = bwd ? cin : cout, k_in = bwd ? cout : cin;
   const int nchunks = (k_in + CK - 1) / CK, NB = blocks_for(n_out);
-  const int blk = f % NB, ks = (f / NB) % KS, tap = (f / (KS * NB)) % 9, chunk = (f / (9 * KS * NB)) % nchunks, tile = f / (9 * KS * NB * nchunks);
+  const int blk = f % NB, tap = (f / NB) % 9, chunk = (f / (9 * NB)) % nchunks, tile = f / (9 * NB * nchunks);
   const int o = (tile * NB + blk) * 32 + (lane & 31);
-  const int i0 = chunk * CK + ks * 16 + (lane >> 5) * 8;
+  const int i0 = chunk * CK + (lane >> 5) * 8;
   const int kh = tap / 3, kw = tap % 3;
   float v[8];
 #pragma unroll
@@ -115,9 +112,9 @@ __device__ __forceinline__ f16v mfma(const u4& a, const u4& b, const f16v& c) {
 
 // y (B,Ho,Wo,n_out) = conv3x3(x (B,Hi,Wi,k_in) zero-extended, pack) + bias;  Ho = Hi + 2 pad - 2, pad in 0..2; x, y in the half type
 template <int NB, bool F16>
-__global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsigned short* __restrict__ x, const uint4* __restrict__ pack, const float* __restrict__ bias,
-                                                          int Hi, int Wi, int Ho, int Wo, int k_in, int n_out, int pad, int tiles_x, int tiles_y,
-                                                          unsigned short* __restrict__ y) {
+__global__ __launch_bounds__(NT, MINWG) void conv_half_kernel(const unsigned short* __restrict__ x, const uint4* __restrict__ pack, const float* __restrict__ bias,
+                                                              int Hi, int Wi, int Ho, int Wo, int k_in, int n_out, int pad, int tiles_x, int tiles_y,
+                                                              unsigned short* __restrict__ y) {
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned char* const s_b = smem + A_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -134,8 +131,8 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
   const char* pk = reinterpret_cast<const char*>(pack) + (size_t)ntile * nchunks * b_bytes<NB>();
 
   // this thread's halo items: item i = tid + j * NT -> pixel i / OCT, channel octet i % OCT.  Their offsets are recomputed per chunk from
-  // the item index (a dozen integer instructions per item against 36 MFMAs per chunk) instead of living in 2 * A_PRE registers across the
-  // MFMA block: with the fragments read one tap ahead only (DD_CH_TAP_FENCE) the kernel fits 128 VGPRs -- four workgroups per CU.
+  // the item index (a dozen integer instructions per item against 18*NB MFMAs per chunk) instead of living in 2 * A_PRE registers across
+  // the MFMA block.
   auto item_lds = [&](int j) -> int {          // byte offset in the halo plane, or -1 beyond the halo
     const int i = tid + j * NT, px = i / OCT, q = i % OCT;
     return px < HN ? px * PSTR + q * 16 : -1;
@@ -150,10 +147,7 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
   // first pixel and are zeroed when staged; the weight items beyond a partial last round re-read the chunk's first): straight-line code,
   // the compiler's counted waits stay exact.
   u4 pre[A_PRE];
-#ifdef DD_CH_DEEP
-  u4 pre1[A_PRE];              // a second halo in flight: the halo of chunk c + 2 is fetched while chunk c is multiplied (weights: c + 1, from L2)
-#endif
-  auto fetch_a = [&](int chunk, u4 (&pre)[A_PRE]) {
+  auto fetch_a = [&](int chunk) {
 #pragma unroll
     for (int j = 0; j < A_PRE; ++j) {
       const int c0 = chunk * CK + (((tid + j * NT) % OCT) << 3);
@@ -162,7 +156,7 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
       pre[j] = *reinterpret_cast<const u4*>(xb + off);
     }
   };
-  auto stage_a = [&](int chunk, const u4 (&pre)[A_PRE]) {
+  auto stage_a = [&](int chunk) {
 #pragma unroll
     for (int j = 0; j < A_PRE; ++j) {
       const int lo = item_lds(j);
@@ -201,7 +195,7 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
 
-  // A fragment of this lane: tile row 2*wave + m, column lane & 31, channels step * 16 + (lane >> 5) * 8 .. + 7 of the chunk
+  // A fragment of this lane: tile row 2*wave + m, column lane & 31, channels (lane >> 5) * 8 .. + 7 of the chunk
   const unsigned char* a_lane = smem + ((2 * wave) * HW + (lane & 31)) * PSTR + (lane >> 5) * 16;
   const unsigned char* b_lane = s_b + lane * 16;
 
@@ -209,66 +203,32 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int ty = tap / 3, tx = tap % 3;
+      u4 af[2], bf[NB];
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        u4 af[2], bf[NB];
+      for (int m = 0; m < 2; ++m) af[m] = *reinterpret_cast<const u4*>(a_lane + ((m + ty) * HW + tx) * PSTR);
 #pragma unroll
-        for (int m = 0; m < 2; ++m) af[m] = *reinterpret_cast<const u4*>(a_lane + ((m + ty) * HW + tx) * PSTR + ks * 32);
+      for (int n = 0; n < NB; ++n) bf[n] = *reinterpret_cast<const u4*>(b_lane + (tap * NB + n) * FRAG);
 #pragma unroll
-        for (int n = 0; n < NB; ++n) bf[n] = *reinterpret_cast<const u4*>(b_lane + ((tap * KS + ks) * NB + n) * FRAG);
+      for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-          for (int n = 0; n < NB; ++n) acc[m][n] = mfma<F16>(af[m], bf[n], acc[m][n]);
-      }
-#ifdef DD_CH_TAP_FENCE
-      if (tap % DD_CH_TAP_FENCE == DD_CH_TAP_FENCE - 1) __builtin_amdgcn_sched_barrier(0);     // caps the fragments read ahead (registers)
-#endif
+        for (int n = 0; n < NB; ++n) acc[m][n] = mfma<F16>(af[m], bf[n], acc[m][n]);
     }
   };
   const int last = nchunks - 1;
-#ifdef DD_CH_DEEP
-  // Chunks in pairs, two halo register sets: set 0 holds the even chunks, set 1 the odd ones; an odd chunk count runs one all-zero
-  // chunk more (its halo is staged as zeros: c0 >= k_in; its weights are the last chunk's -- the products vanish).
-  fetch_a(0, pre);
-  fetch_a(1, pre1);
-  fetch_b(0);
-  for (int chunk = 0; chunk < nchunks; chunk += 2) {
-    lds_barrier();
-    stage_a(chunk, pre);
-    stage_b();
-    lds_barrier();
-    fetch_a(chunk + 2, pre);
-    fetch_b(min(chunk + 1, last));
-    __builtin_amdgcn_sched_barrier(0);
-    multiply();
-    __builtin_amdgcn_sched_barrier(0);
-    lds_barrier();
-    stage_a(chunk + 1, pre1);
-    stage_b();
-    lds_barrier();
-    fetch_a(chunk + 3, pre1);
-    fetch_b(min(chunk + 2, last));
-    __builtin_amdgcn_sched_barrier(0);
-    multiply();
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#else
-  fetch_a(0, pre);
+  fetch_a(0);
   fetch_b(0);
   for (int chunk = 0; chunk < nchunks; ++chunk) {
     lds_barrier();                         // the previous chunk's fragment reads are done
-    stage_a(chunk, pre);
+    stage_a(chunk);
     stage_b();
     lds_barrier();
-    fetch_a(min(chunk + 1, last), pre);    // (the last chunk re-reads itself: no branch around the loads)
+    fetch_a(min(chunk + 1, last));         // (the last chunk re-reads itself: no branch around the loads)
     fetch_b(min(chunk + 1, last));
     __builtin_amdgcn_sched_barrier(0);     // the loads go out IN FRONT of the MFMAs (left alone, the scheduler sinks them behind the block:
                                            // shorter live ranges, and the whole round trip exposed in front of the next staging)
     multiply();
     __builtin_amdgcn_sched_barrier(0);     // ... and the waits for them stay behind the block
   }
-#endif
 
   // C layout of 32x32: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
 #pragma unroll
@@ -292,7 +252,7 @@ __global__ __launch_bounds__(NT, DD_CH_MINWG) void conv_half_kernel(const unsign
 
 static size_t pack_bytes(int n_out, int k_in) {
   const int NB = blocks_for(n_out), tiles = (n_out + 32 * NB - 1) / (32 * NB), nchunks = (k_in + CK - 1) / CK;
-  return (size_t)tiles * nchunks * 9 * KS * NB * FRAG;
+  return (size_t)tiles * nchunks * 9 * NB * FRAG;
 }
 
 template <int NB, bool F16>

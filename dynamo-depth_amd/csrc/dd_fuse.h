@@ -20,13 +20,11 @@
 
 namespace dd {
 
-#ifndef DD_TH
-#define DD_TH 16         // 16x32 tiles = 512 threads, ~77 KB LDS: two workgroups per CU (16 waves) whose barrier-separated
-#define DD_TW 32         // stages interleave; measured 5-9 % faster than one 16x64 / 1024-thread workgroup per CU
-#define DD_MIN_WAVES 4   // <= 128 VGPRs so that both workgroups fit
-#endif
-constexpr int TH = DD_TH;         // tile height (target pixels); multiple of 8 (coarsest scale block)
-constexpr int TW = DD_TW;         // tile width
+// 16x32 tiles = 512 threads, ~77 KB LDS: two workgroups per CU (16 waves) whose barrier-separated stages interleave; measured
+// 5-9 % faster than one 16x64 / 1024-thread workgroup per CU
+constexpr int TH = 16;            // tile height (target pixels); multiple of 8 (coarsest scale block)
+constexpr int TW = 32;            // tile width
+constexpr int MIN_WAVES = 4;      // the tile kernel's launch bound (waves per SIMD): <= 128 VGPRs so that both workgroups fit
 
 // Per-tile low-res gradient footprints (scale >= 1) go to the workspace with plain stores; the combine pass sums the
 // <= 4 tiles that overlap each low-res pixel in a fixed order: deterministic gradients, no device atomics.

@@ -32,10 +32,6 @@
 #include "dd_fuse.h"
 #include "dd_pair.h"
 
-#ifdef DD_EXP_NOBARRIER     // timing experiment only (wrong results): what do the workgroup barriers cost?
-#define __syncthreads() do { } while (0)
-#endif
-
 namespace dd {
 
 // TH x TW tiles (dd_fuse.h: 16x32 = 512 threads, ~77 KB LDS, two workgroups per CU)
@@ -55,15 +51,6 @@ constexpr int NRED = 30;          // photo, n_warp, cons[2], delta[2], gT[2][12]
 constexpr int LOWH = RH / 2 + 2, LOWW = RW / 2 + 2;           // staged low-res region (scale >= 1) incl. halo taps
 constexpr int LOWN = LOWH * LOWW;
 static_assert(RING <= NT && CRING <= NT, "one pass over the halo ring");
-#ifndef DD_EXP_TAPS
-#define DD_EXP_TAPS 0
-#endif
-#ifndef DD_RING_LDS
-#define DD_RING_LDS 0            // 1 (experiment, round 5): the halo ring's source taps go global -> LDS directly and share the owners' memory
-#endif                           // round trip in stage A -- correct (same values) and SLOWER: profiles/r05_photo_ring_through_lds.txt
-constexpr int RING_WAVES = (RING + 63) / 64;
-constexpr int RING_STAGE_OFF = (9 * LOWN + 63) / 64 * 64;                    // floats: behind the staged low-res inputs
-constexpr int RING_STAGE_FLOATS = (24 + 8) * RING_WAVES * 64;                // 24 taps + four f2 weights per ring pixel
 static_assert(TH % 8 == 0 && TW % 16 == 0 && NT % 64 == 0 && NT <= 1024, "tile shape");
 static_assert(LOWN <= 256 && NT >= 512, "low-res staging takes two planes per pass, 256 threads each");
 static_assert(NWAVES * 4 >= NRED && NWAVES * 5 >= NRED + NSMOOTH && NWAVES * 5 == DD_PARTIAL_STRIDE && REC_SMOOTH == NRED,
@@ -96,11 +83,7 @@ __device__ __forceinline__ float ldg(const float* base, unsigned byte_off) {
 // Keeps the instruction stream in source order across this point: the asm memory clobber pins the loads at instruction
 // selection, sched_barrier pins everything in the machine scheduler.  Used to cap the number of LDS values in flight where
 // the default schedule (all loads first) would spill the per-pixel state.
-#ifndef DD_NO_ORDER
 #define DD_ORDER() do { asm volatile("" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DD_ORDER() do { } while (0)
-#endif
 // ... and an accumulator named here has to be complete at this point (its arithmetic cannot sink below the loads that follow)
 #define DD_PIN(x) asm volatile("" : "+v"(x))
 
@@ -206,7 +189,6 @@ struct LdsLayout {
   signed char sel[(R1N + 15) / 16 * 16];   // selected frame per centre (-1: identity won / outside the image)
 };
 static_assert(9 * TH * TW * sizeof(float) <= sizeof(f2) * 3 * R2N + sizeof(float) * 3 * R2N, "gradient planes must fit into pred+tgt");
-static_assert((RING_STAGE_OFF + RING_STAGE_FLOATS) * sizeof(float) <= sizeof(f2) * 9 * R1N, "the ring's tap staging must fit into the coefficient planes");
 static_assert(9 * TH * FPW_MAX * sizeof(float) <= sizeof(f2) * 9 * R1N, "x-reduced planes must fit into coef");
 static_assert(sizeof(LdsLayout) >= NT * NWAVES * 4 * sizeof(float), "the transposed reduction spans the whole layout");
 static_assert(sizeof(LdsLayout) <= 80 * 1024, "two workgroups per CU");
@@ -279,9 +261,6 @@ __global__ __launch_bounds__(NT) void photo_identity_kernel(const float* __restr
   }
 }
 
-#ifndef DD_MIN_WAVES
-#define DD_MIN_WAVES 1
-#endif
 // OUT: the materialised outputs of a log step (colour, sample grid, depth, ...) are written; the training step proper
 // runs the instantiation without them (fewer live pointers: no scalar-register spills).
 // SHARED: both frames read the same flow tensor (the sign rides on ts) and the same mask tensor, and their gradients
@@ -290,8 +269,8 @@ __global__ __launch_bounds__(NT) void photo_identity_kernel(const float* __restr
 // mask (tools.py:311-326, Trainer.py:355-359,380-381,401-402) is evaluated in the store stage -- the target tile sits in LDS, the
 // thread holds its pixel's gradient -- and its gradient is added before the pixel's ONE store; seven more block sums.
 template <int MODE, bool AUTOMASK, bool GRAD, bool SHARED, bool OUT, bool SMOOTH = false>
-__global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPhotoArgs a, const DepthParams dp, const ImageDims dim,
-                                                                     const FootprintInfo fp, const FuseInfo fuse, const SideInfo side) {
+__global__ __launch_bounds__(NT, MIN_WAVES) void photo_tile_kernel(const DDPhotoArgs a, const DepthParams dp, const ImageDims dim,
+                                                                   const FootprintInfo fp, const FuseInfo fuse, const SideInfo side) {
   static_assert(!SMOOTH || (GRAD && (SHARED || MODE == MODE_RIGID)), "fused smoothness: gradient pass, one tensor per group");
   extern __shared__ __align__(16) unsigned char smem_raw[];
   LdsLayout& S = *reinterpret_cast<LdsLayout*>(smem_raw);
@@ -301,32 +280,11 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   const int tid = threadIdx.x;
   const int H = a.H, W = a.W, N = H * W;
   const int tiles_x = (W + TW - 1) / TW;
-#ifdef DD_SCALE_INNER
-  // (build switch, round 6) ONE-dimensional grid: ntiles * B * S tile workgroups, then the side workgroups.  Workgroup i runs on XCD i % 8;
-  // every XCD takes a contiguous range of the work list ordered (image, tile, scale) with the SCALE innermost: the three scale passes of a
-  // tile -- same target tile, neighbouring source pixels -- follow one another on one XCD and share its L2 (the default order launches them
-  // 2 880 workgroups apart: the launch fetches its 60 MB of frames four times over).  A bijection: results do not depend on it.
-  const int ntiles = tiles_x * ((H + TH - 1) / TH), work = ntiles * a.B * a.num_scales;
-  const int wid = blockIdx.x;
-  const bool side_wg = wid >= work;
-  int b, si, tile = 0;
-  if (side_wg) { b = (wid - work) % a.B; si = (wid - work) / a.B; }
-  else {
-    const int x = wid & 7, base = work >> 3, extra = work & 7;
-    const int w = x * base + min(x, extra) + (wid >> 3);
-    si = w % a.num_scales;
-    tile = (w / a.num_scales) % ntiles;
-    b = w / (a.num_scales * ntiles);
-  }
-  const DDPhotoScale& sc = a.scale[si];
-  if (SMOOTH && side.on && side_wg) {
-#else
   const int b = blockIdx.y;
   const int si = blockIdx.z;
   const DDPhotoScale& sc = a.scale[si];
   const int ntiles = SMOOTH ? (int)gridDim.x - side.on : (int)gridDim.x;
   if (SMOOTH && side.on && (int)blockIdx.x == ntiles) {
-#endif
     // ---- the extra workgroup of (image b, scale si): RANSAC candidates + disparity sum (dd_fuse.h) -- nothing of the tile path ----
     const SideScale& ss = side.sc[si];
     const int h = sc.h, w = sc.w, n = h * w;
@@ -368,7 +326,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   // XCD-aware tile order: workgroup i runs on XCD i % 8 (each XCD has its own L2).  Give every XCD a contiguous
   // band of the image so that neighbouring tiles -- which re-read each other's 2-pixel halo and the same source rows --
   // share an L2 instead of each missing separately.  Pure permutation of blockIdx.x: correctness does not depend on it.
-#ifndef DD_SCALE_INNER
   int tile = blockIdx.x;
   {
     // XCD x = blockIdx.x % 8 runs workgroups x, x + 8, ...: it gets the contiguous band that starts behind the bands of XCDs 0..x-1
@@ -377,7 +334,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     const int x = tile & 7, base = ntiles >> 3, extra = ntiles & 7;
     tile = x * base + min(x, extra) + (tile >> 3);
   }
-#endif
   const int X0 = (tile % tiles_x) * TW, Y0 = (tile / tiles_x) * TH;
   const int shift = sc.shift, h = sc.h, w = sc.w, n = h * w;
   const float ratio = 1.f / static_cast<float>(1 << shift);
@@ -393,7 +349,7 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   // global_load_dwordx3 per bilinear tap and frame, 8 gathers per pixel instead of 24 and a third of the cache lines they touch:
   // the gather's divergence, not its latency, is what the warp stage pays for (profiles/r05_photo_gather_ablation.txt) -- else the
   // planar tensors of the reference boundary.
-  const bool packed = !DD_RING_LDS && a.source_packed[0] != nullptr && a.source_packed[1] != nullptr;
+  const bool packed = a.source_packed[0] != nullptr && a.source_packed[1] != nullptr;
   const float* src0_g = (packed ? a.source_packed[0] : a.source[0]) + (size_t)b * 3 * N;
   const float* src1_g = (packed ? a.source_packed[1] : a.source[1]) + (size_t)b * 3 * N;
   const float* disp_g = sc.disp + (size_t)b * n;
@@ -591,12 +547,8 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     const SampleCoord2 scd = pixel_geometry(X, Y, d, c, m, Z_out, g, sd);
     // all 24 source taps are issued before any is consumed (memory-level parallelism)
     f2 v00[3], v01[3], v10[3], v11[3];
-#if DD_EXP_TAPS == 1      // timing experiment only (wrong results): every tap reads the pixel's own position -- what does the gather's divergence cost?
-    const unsigned a00 = (unsigned)(__mul24(Y, W) + X) * 4u, a01 = a00, a10 = a00, a11 = a00, b00 = a00, b01 = a00, b10 = a00, b11 = a00;
-#else
     const unsigned a00 = scd.o00[0], a01 = a00 + scd.dxb[0], a10 = a00 + scd.dyb[0], a11 = a10 + scd.dxb[0];
     const unsigned b00 = scd.o00[1], b01 = b00 + scd.dxb[1], b10 = b00 + scd.dyb[1], b11 = b10 + scd.dxb[1];
-#endif
     if (packed) {
       const char* q0 = reinterpret_cast<const char*>(src0_g);
       const char* q1 = reinterpret_cast<const char*>(src1_g);
@@ -615,18 +567,10 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
       for (int ch = 0; ch < 3; ++ch) {
         const float* p0 = src0_g + ch * (unsigned)N;
         const float* p1 = src1_g + ch * (unsigned)N;
-#if DD_EXP_TAPS == 2      // timing experiment only (wrong results): no source loads at all
-        const float fk = __builtin_bit_cast(float, a00 + b01 + (unsigned)ch);
-        v00[ch] = mk2(fk, fk + 1.f); v01[ch] = mk2(fk + 2.f, fk); v10[ch] = mk2(fk, fk + 3.f); v11[ch] = mk2(fk + 4.f, fk);
-#elif DD_EXP_TAPS == 3    // timing experiment only (wrong results): one load per frame and channel instead of four
-        v00[ch] = mk2(ldg(p0, a00), ldg(p1, b00));
-        v01[ch] = v00[ch] + sp2(__builtin_bit_cast(float, a01)); v10[ch] = v00[ch] + sp2(__builtin_bit_cast(float, a10)); v11[ch] = v00[ch] + sp2(__builtin_bit_cast(float, b11));
-#else
         v00[ch] = mk2(ldg(p0, a00), ldg(p1, b00));
         v01[ch] = mk2(ldg(p0, a01), ldg(p1, b01));
         v10[ch] = mk2(ldg(p0, a10), ldg(p1, b10));
         v11[ch] = mk2(ldg(p0, a11), ldg(p1, b11));
-#endif
       }
     }
 #pragma unroll
@@ -634,29 +578,12 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     if (store) store_warped(X, Y, ry, rx, xval);
   };
 
-#ifdef DD_DEPHASE         // experiment (round 5): the two workgroups of a CU start together and, with equal lifetimes, stay in phase (both in
-  {                       // the load-bound warp stage, then both in the VALU-bound stages): delay every second first-generation workgroup
-    const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if (lin < 512u && ((lin >> DD_DEPHASE) & 1u)) {
-#pragma unroll 1
-      for (int k = 0; k < DD_DEPHASE_N; ++k) __builtin_amdgcn_s_sleep(127);
-    }
-  }
-#endif
   DD_ISA("warp_halo 0.5");
-#ifdef DD_PRIO_WARP       // experiment (round 5): waves 0-3 carry the workgroup's critical path (ring pass, then their own pixel)
-  if (tid < 256) __builtin_amdgcn_s_setprio(DD_PRIO_WARP);
-#endif
   // Halo ring: one pixel, both frames, per thread of waves 0-3, forward only, as a pass of its own IN FRONT of the owners' pass (its
   // transient registers are gone before the owner state comes alive): waves 0-3 go through inputs -> geometry -> 24 gathered taps ->
   // interpolation twice, one after the other, while waves 4-7 wait at the barrier (the warp stage is 46-66 % of a workgroup's life).
-  // -DDD_RING_LDS=1 (experiment): the ring's taps go global -> LDS directly (global_load_lds_dword: no VGPR holds them), its four tap
-  // weights wait in LDS too, the owner's pass is issued right behind -- ONE memory round trip covers both -- and the ring is interpolated
-  // from LDS afterwards (staging area: the coefficient planes', not live before stage B; the owner's inputs are read first: the compiler
-  // puts a full vmcnt(0) in front of every LDS read behind an LDS-direct load).  Same values (the parity tests pass), but 4 % SLOWER
-  // without spills (disp_init, motion_init) and 25 % slower where the ring's finish meets the live owner state (fine_tune: 15 VGPRs
-  // spilled): the two round trips of waves 0-3 are NOT what the warp stage waits for -- it is throughput (issue slots shared with the
-  // CU's other workgroup, the texture path), not the latency of a dependent chain.
+  // Sending the ring's taps global -> LDS directly, so that ONE memory round trip covers ring and owner, gave the same values and was
+  // 4-25 % slower (profiles/r05_photo_ring_through_lds.txt): the stage waits for load throughput, not for the latency of the two passes.
   auto ring_pixel = [&](int r, int& ry, int& rx) -> bool {      // region position of ring pixel r; is it one (inside the image)?
     ry = rx = 0;
     if (r < 2 * RW) { ry = r / RW; rx = r % RW; }
@@ -670,40 +597,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   const int ring_Y = Y0 - 2 + ring_ry, ring_X = X0 - 2 + ring_rx;
   float d_own;
   f2 c_own[3], m_own;
-#if DD_RING_LDS
-  float* const ring_taps = S.low + RING_STAGE_OFF;                               // [24 taps][RING_WAVES][64 lanes]
-  f2* const ring_wgt = reinterpret_cast<f2*>(ring_taps + 24 * RING_WAVES * 64);   // [4][RING_WAVES * 64]
-  pixel_inputs(oX, oY, d_own, c_own, m_own);
-  if (ring_on) {
-    float d, Zu;
-    f2 c[3], m;
-    PairGeom gu;
-    PairSide su;
-    pixel_inputs(ring_X, ring_Y, d, c, m);
-    const SampleCoord2 scd = pixel_geometry(ring_X, ring_Y, d, c, m, Zu, gu, su);
-    ring_wgt[0 * RING_WAVES * 64 + tid] = scd.w00;
-    ring_wgt[1 * RING_WAVES * 64 + tid] = scd.w01;
-    ring_wgt[2 * RING_WAVES * 64 + tid] = scd.w10;
-    ring_wgt[3 * RING_WAVES * 64 + tid] = scd.w11;
-    const unsigned a00 = scd.o00[0], a01 = a00 + scd.dxb[0], a10 = a00 + scd.dyb[0], a11 = a10 + scd.dxb[0];
-    const unsigned b00 = scd.o00[1], b01 = b00 + scd.dxb[1], b10 = b00 + scd.dyb[1], b11 = b10 + scd.dxb[1];
-    float* const dst = ring_taps + __builtin_amdgcn_readfirstlane(tid & ~63);    // the hardware adds lane * 4
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const char* p0 = reinterpret_cast<const char*>(src0_g + ch * (unsigned)N);
-      const char* p1 = reinterpret_cast<const char*>(src1_g + ch * (unsigned)N);
-      float* const dk = dst + ch * 8 * RING_WAVES * 64;
-      __builtin_amdgcn_global_load_lds(p0 + a00, dk + 0 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p1 + b00, dk + 1 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p0 + a01, dk + 2 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p1 + b01, dk + 3 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p0 + a10, dk + 4 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p1 + b10, dk + 5 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p0 + a11, dk + 6 * RING_WAVES * 64, 4, 0, 0);
-      __builtin_amdgcn_global_load_lds(p1 + b11, dk + 7 * RING_WAVES * 64, 4, 0, 0);
-    }
-  }
-#else
   if (ring_on) {
     float d, Zu;
     f2 c[3], m, du[3], dw[3], xv[3];
@@ -713,7 +606,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     warp_pixel(ring_X, ring_Y, ring_ry, ring_rx, true, d, c, m, Zu, gu, su, du, dw, xv);
   }
   pixel_inputs(oX, oY, d_own, c_own, m_own);
-#endif
   // owner state (one pixel per thread)
   float Zs;
   f2 mval, dvx[3], dvy[3];
@@ -728,28 +620,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     f2 xval[3];
     warp_pixel(oX, oY, ly + 2, lx + 2, own, d_own, c_own, m_own, Zs, geo, sd, dvx, dvy, xval);
     mval = m_own;
-#if DD_RING_LDS
-    DD_ISA("warp_halo_finish 0.5");
-    int tid2 = tid, fy, fx;
-    asm volatile("" : "+v"(tid2));             // the ring position is formed again (five registers less across the owner's pass)
-    if (ring_pixel(tid2, fy, fx)) {
-      const int ring_ry = fy, ring_rx = fx, ring_Y = Y0 - 2 + fy, ring_X = X0 - 2 + fx;
-      __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): the ring's taps have landed (they were issued in front of the owner's)
-      f2 xv[3];
-      const f2 w00 = ring_wgt[0 * RING_WAVES * 64 + tid], w01 = ring_wgt[1 * RING_WAVES * 64 + tid];
-      const f2 w10 = ring_wgt[2 * RING_WAVES * 64 + tid], w11 = ring_wgt[3 * RING_WAVES * 64 + tid];
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float* tk = ring_taps + ch * 8 * RING_WAVES * 64 + tid;
-        const f2 v00 = mk2(tk[0 * RING_WAVES * 64], tk[1 * RING_WAVES * 64]), v01 = mk2(tk[2 * RING_WAVES * 64], tk[3 * RING_WAVES * 64]);
-        const f2 v10 = mk2(tk[4 * RING_WAVES * 64], tk[5 * RING_WAVES * 64]), v11 = mk2(tk[6 * RING_WAVES * 64], tk[7 * RING_WAVES * 64]);
-        xv[ch] = v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11;         // sample_taps2's value
-        DD_PIN(xv[ch]);
-        DD_ORDER();          // one channel's eight taps in registers at a time: the owner state is alive here
-      }
-      store_warped(ring_X, ring_Y, ring_ry, ring_rx, xv);
-    }
-#endif
     if (OUT && own) {
       if (sc.out_depth) sc.out_depth[(size_t)b * N + op] = Zs;
 #pragma unroll
@@ -796,9 +666,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
       }
     }
   }
-#ifdef DD_PRIO_WARP
-  __builtin_amdgcn_s_setprio(0);
-#endif
   DD_ISA("lr_down 1.0");
   if (MODE == MODE_FLOW_MASK && shift > 0) {
     const bool left = own && ((oX & ((1 << shift) - 1)) == (1 << (shift - 1)) - 1) && down_tap(oY, shift);
@@ -815,9 +682,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   DD_STAGE_MARK(2);
 
   DD_ISA("ssim_own 1.0");
-#ifdef DD_PRIO_SSIM       // experiment: the VALU-dense stages issue ahead of the other workgroup's load-bound stages
-  __builtin_amdgcn_s_setprio(DD_PRIO_SSIM);
-#endif
   // ---- stage B: SSIM + L1, selection, loss, backward coefficients ------------------------------------
   float acc_photo = 0.f, acc_nwarp = 0.f;
   // One centre, branch-free.  A centre outside the image evaluates the window of the tile's first pixel instead (always
@@ -826,12 +690,7 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   // the selected loss.
   auto centre = [&](int ci, int li, bool in, float idb, float& best_out) -> int {
     const float wgt = sc.w_photo * alpha * (1.f / 27.f);     // the coefficients come out weighted
-#ifdef DD_EXP_NO_SSIM      // timing experiment only (wrong results): what do the SSIM window sums cost?
-    const f2 rho = S.pred[in ? li : 2 * RW + 2] * sp2(wgt) + sp2(S.tgt[li]);
-    if (GRAD) { for (int k = 0; k < 9; ++k) S.coef[ci + k * R1N] = rho; }
-#else
     const f2 rho = rho_pair<GRAD>(S.pred, S.tgt, in ? li : 2 * RW + 2, alpha, wgt, S.coef + ci);
-#endif
     const bool second = rho[1] < rho[0];
     float best = second ? rho[1] : rho[0];
     bool warped = in;
@@ -858,9 +717,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
     centre(hci, hli, hc_in, id_ring, best);
   }
 
-#ifdef DD_PRIO_SSIM
-  __builtin_amdgcn_s_setprio(0);
-#endif
   DD_ISA("stageL 0.25");
   // ---- stage L: c_consistency and disp_mag on the tile's low-res pixels (scale >= 1) -------------------
   if (MODE == MODE_FLOW_MASK && shift > 0) {
@@ -894,9 +750,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
   DD_STAGE_MARK(3);
 
   DD_ISA("gather 1.0");
-#ifdef DD_PRIO_GATHER
-  __builtin_amdgcn_s_setprio(DD_PRIO_GATHER);
-#endif
   // ---- stage C: backward ------------------------------------------------------------------------------
   f2 gTacc[12];
 #pragma unroll
@@ -985,9 +838,6 @@ __global__ __launch_bounds__(NT, DD_MIN_WAVES) void photo_tile_kernel(const DDPh
         else { gch[CHN::MASK0] = pg.gm[0]; gch[CHN::MASK0 + 1] = pg.gm[1]; }
       }
     }
-#ifdef DD_PRIO_GATHER
-    __builtin_amdgcn_s_setprio(0);
-#endif
     DD_ISA("store 1.0");
     auto grad_ptr = [&](int ch) -> float* {
       if (ch == 0) return sc.g_disp + (size_t)b * n;
@@ -1342,11 +1192,7 @@ static bool timer_slot(hipStream_t stream, hipEvent_t*& pair) {
 template <int MODE, bool AUTOMASK, bool GRAD, bool SHARED, bool OUT, bool SMOOTH>
 static int launch_tile(const DDPhotoArgs& a, const FuseInfo& fuse, const SideInfo& side, hipStream_t stream) {
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + TH - 1) / TH, tiles = tiles_x * tiles_y;
-#ifdef DD_SCALE_INNER
-  dim3 grid(tiles * a.B * a.num_scales + ((SMOOTH && side.on) ? a.B * a.num_scales : 0));
-#else
   dim3 grid(tiles + ((SMOOTH && side.on) ? 1 : 0), a.B, a.num_scales);
-#endif
   auto kern = photo_tile_kernel<MODE, AUTOMASK, GRAD, SHARED, OUT, SMOOTH>;
   static dd::LdsAttrOnce lds_attr;          // per instantiation and device (dd_attr.h)
   if (const int rc = lds_attr.ensure(reinterpret_cast<const void*>(kern), (int)((int)lds_bytes(SMOOTH)))) return rc;

@@ -1895,7 +1895,7 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
         sparsity_grad_body<SPG_PXT>(bx, by, gx, sc.delta[f], sc.delta_sum[f], sc.prob[f], B, n, inv_total, sc.w_sparsity[f], ws + off.sp_part[s][f],
                                     sc.g_prob[f], res + 10 + 2 * f);
       break;
-    case K_GSCORE:
+    case K_GSCORE:      // (no plan adds this task any more: the scoring runs on the matrix pipe, in the post kernel)
       ground_score_body(bx, by, gx, sc.disp, sc.inv_K, ws + off.g_cand[s], B, h, w, rows, a.max_it, a.tol, dp,
                         reinterpret_cast<int*>(ws + off.g_counts[s]), reinterpret_cast<int*>(ws + off.g_cpart[s]));
       break;
@@ -1975,9 +1975,6 @@ struct RegPlan {
 // does the smoothness of this launch qualify for smooth_quad_kernel?  Every scale that smooths anything must smooth the same number
 // of channels (1 | 3 | 4 | 5: what the four phases produce with shared tensors) in rows of whole, 16-byte aligned quads.
 static int quad_channels(const DDRegArgs& a) {
-#ifdef DD_REG_NO_QUAD
-  return 0;
-#endif
   auto aligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; };
   int common = 0;
   for (int s = 0; s < a.num_scales; ++s) {
@@ -2103,9 +2100,6 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
       const int score_blocks = (rows * sc.w + GS_SLABS * RT_NT - 1) / (GS_SLABS * RT_NT);
       p.off.g_cpart[s] = take((size_t)a.B * score_blocks * a.max_it);
       bad |= add(0, K_GCAND, s, 0, (a.B * a.max_it + RT_NT - 1) / RT_NT, 1);
-#ifdef DD_REG_SCORE_VALU
-      bad |= add(1, K_GSCORE, s, 0, score_blocks, a.B);
-#else
       {
         ScoreScale& q = p.score.sc[s];
         q.disp = sc.disp; q.inv_K = sc.inv_K; q.cand = a.workspace + p.off.g_cand[s];
@@ -2113,7 +2107,6 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
         q.h = sc.h; q.w = sc.w; q.rows = rows; q.gx = score_blocks; q.first = p.score_blocks;
         p.score_blocks += score_blocks * a.B;
       }
-#endif
       bad |= add(4, K_GFOLD, s, 0, 1, 1);
     }
   }
