@@ -1,13 +1,18 @@
-"""torch.autograd bridges onto the C ABI (libdynamo_hip.so): one Function per tools.py operator.
+"""torch.autograd bridges onto the C ABI (libdynamo_hip.so): first the loss operators of tools.py (fp32 GPU tensors only, anything else
+raises: _dev), then the networks' layers -- the convolution Functions, the decoder glue, LiteMono's blocks, the norms and slices.
 
-torch is used here only for device memory, the current HIP stream and the autograd tape; every
-computation is a HIP kernel behind include/dynamo_hip.h.  There is no CPU path: CPU tensors raise.
+Beside a Function stand its `*_ok` predicate (shapes, types, layout and the DD_* switches, all read at call time), its `*_calls()`
+launch counter and its wrapper.  A wrapper whose operator ATen also has (reflect_pad1, layer_norm_last, ...) hands it what the kernel
+does not cover; a Function applied directly never falls back.  The launch and gradient helpers that several Functions share are the
+private functions up front; MfmaConvFn's weight-pack batching is pack_many.py.  torch provides device memory, the current HIP stream,
+the tape and the library GEMMs / convolutions named where they are used; everything else is a HIP kernel behind include/dynamo_hip.h.
 """
 import os
 
 import torch
 
 from . import lib as L
+from .pack_many import PackSet, _ACTIVE_PACK_SETS, _pack_many_on, pack_many_launches, pack_weights_once_per_forward  # noqa: F401 (re-exported)
 
 
 def _dev(t, name="tensor"):
@@ -42,6 +47,44 @@ def _ws_bytes(name, *dims):
     if n is None:
         n = _WS_BYTES[key] = int(getattr(L.load(), name)(*dims))
     return n
+
+
+def _nhwc_empty(B, Cc, H, W, device, *, dtype=torch.float32):
+    """An uninitialised (B,Cc,H,W) tensor on dense channels-last memory: strides (H*W*Cc, 1, W*Cc, Cc) for every Cc, 1 included."""
+    return torch.empty((B, H, W, Cc), dtype=dtype, device=device).permute(0, 3, 1, 2)
+
+
+def _channel_sum(g, rows, cout, code, stream):
+    """fp32 (cout,) column sums of the dense (rows, cout) matrix at g (element type `code`), in a fixed order: the bias gradients."""
+    gb = torch.empty(cout, dtype=torch.float32, device=g.device)
+    ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), g.device)
+    L.check(L.load().dd_channel_sum_nhwc_t(_p(g), rows, cout, _p(gb), code, _p(ws), stream), "dd_channel_sum_nhwc_t")
+    return gb
+
+
+def _wgrad_1x1(go, x, w, B, H, W):
+    """(B*H*W, cout), (B*H*W, cin) -> (cout, cin): a Linear's weight gradient by MIOpen's 1x1 implicit GEMM on channels-last views."""
+    cout, cin = w.shape
+    _, gw, _ = torch.ops.aten.convolution_backward(go.view(B, H, W, cout).permute(0, 3, 1, 2), x.view(B, H, W, cin).permute(0, 3, 1, 2),
+                                                   w.view(cout, cin, 1, 1), None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])
+    return gw.reshape(cout, cin)
+
+
+def _wgrad_3x3_library(g, x, w_like, pad):
+    """The library's weight gradient of a 3x3 stride-1 convolution (only the shape, type and layout of w_like are read)."""
+    return torch.ops.aten.convolution_backward(g, x, w_like, None, (1, 1), (pad, pad), (1, 1), False, [0, 0], 1, (False, True, False))[1]
+
+
+def _conv3x3_s1(x, weight, stride, padding, dilation, groups, allowed):
+    """A plain 3x3 convolution: stride 1, dilation 1, one group, padding one of `allowed`, weight and input agreeing on the channels."""
+    return (tuple(weight.shape[2:]) == (3, 3) and groups == 1 and tuple(stride) == (1, 1) and tuple(dilation) == (1, 1)
+            and tuple(padding) in allowed and x.shape[1] == weight.shape[1])
+
+
+def _below_tile_pixels(B, Ho, Wo, env_name):
+    """Too few output pixels for the 8 x 32-pixel tiles of the 3x3 matrix-pipe kernels to fill the chip (12 x 24 x 80 is still ahead of
+    the library on all three passes, 12 x 12 x 40 is not: profiles/r05_conv_mfma.txt).  mfma_conv_ok and _flat_shape must agree on it."""
+    return Ho < 8 or Wo < 32 or B * Ho * Wo < int(os.environ.get(env_name, "20000"))
 
 
 class BackprojectFn(torch.autograd.Function):
@@ -214,10 +257,9 @@ class ConvBiasFn(torch.autograd.Function):
         if weight.dtype != g.dtype:
             weight = weight.to(g.dtype)
         cin = x.shape[1]
-        head = (ctx.needs_input_grad[0] and cout == 1 and groups == 1 and tuple(weight.shape[2:]) == (3, 3) and tuple(stride) == (1, 1)
-                and tuple(dilation) == (1, 1) and tuple(padding) in ((0, 0), (1, 1)) and g.is_cuda and g.dtype == torch.float32
-                and x.dtype == torch.float32 and cin % 4 == 0 and cin <= 512 and x.is_contiguous(memory_format=torch.channels_last)
-                and not x.is_contiguous())
+        head = (ctx.needs_input_grad[0] and cout == 1 and _conv3x3_s1(x, weight, stride, padding, dilation, groups, ((0, 0), (1, 1)))
+                and g.is_cuda and g.dtype == torch.float32 and x.dtype == torch.float32 and cin % 4 == 0 and cin <= 512
+                and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous())
         mask = (ctx.needs_input_grad[0] and not head, ctx.needs_input_grad[1], False)
         gx, gw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, stride, padding, dilation, False, [0, 0], groups, mask)
         if head:
@@ -233,12 +275,8 @@ class ConvBiasFn(torch.autograd.Function):
                 # channels-last or an arbitrary strided view (slice of a cat gradient): ATen's reduction is pathologically
                 # slow on these (2 ms for (12,9,192,640)); a channels-last copy (if needed) + the HIP kernel is ~50 us
                 gl = g if g.is_contiguous(memory_format=torch.channels_last) else g.contiguous(memory_format=torch.channels_last)
-                lib = L.load()
-                gb = torch.empty(cout, dtype=torch.float32, device=g.device)
-                ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), g.device)
                 B, _, H, W = gl.shape
-                L.check(lib.dd_channel_sum_nhwc_t(_p(gl), B * H * W, cout, _p(gb), DTYPE_CODE[gl.dtype], _p(ws), L.current_stream()),
-                        "dd_channel_sum_nhwc_t")
+                gb = _channel_sum(gl, B * H * W, cout, DTYPE_CODE[gl.dtype], L.current_stream())
             else:
                 gb = g.sum((0, 2, 3))
         if gw is not None and gw.dtype != ctx.saved_tensors[1].dtype:
@@ -271,7 +309,7 @@ class ReduFn(torch.autograd.Function):
         lib = L.load()
         B, Cc, H, W = a.shape
         cout = weight.shape[0]
-        y = torch.empty((B, cout, H, W), dtype=torch.float32, device=a.device).as_strided((B, cout, H, W), (H * W * cout, 1, W * cout, cout))
+        y = _nhwc_empty(B, cout, H, W, a.device)
         wm = weight.reshape(cout, 2 * Cc)                  # (cout, 2C, 1, 1) in either layout is (cout, 2C) rows in memory
         if not wm.is_contiguous():
             wm = wm.contiguous()
@@ -309,12 +347,12 @@ def head_conv_ok(x, weight, stride, padding, dilation, groups):
     reflection padding), 32 or 64 channels-last fp32 input channels."""
     if os.environ.get("DD_STOCK_HEAD_CONV", "0") == "1":
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4):
         return False
-    if weight.shape[0] != 1 or groups != 1 or tuple(stride) != (1, 1) or tuple(dilation) != (1, 1) or tuple(padding) != (0, 0):
+    if weight.shape[0] != 1 or not _conv3x3_s1(x, weight, stride, padding, dilation, groups, ((0, 0),)):
         return False
     B, Cc, Hp, Wp = x.shape
-    if weight.shape[1] != Cc or Hp < 3 or Wp < 3 or torch.is_autocast_enabled() or x.stride() != (Hp * Wp * Cc, 1, Wp * Cc, Cc):
+    if Hp < 3 or Wp < 3 or torch.is_autocast_enabled() or x.stride() != (Hp * Wp * Cc, 1, Wp * Cc, Cc):
         return False
     return bool(L.load().dd_conv_head_supported(Cc))
 
@@ -400,7 +438,7 @@ class SmallConvFn(torch.autograd.Function):
         cout, cin, ks, _ = weight.shape
         B, _, H, W = x.shape
         x = _dense_nhwc(x)
-        y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device).as_strided((B, cout, H, W), (H * W * cout, 1, W * cout, cout))
+        y = _nhwc_empty(B, cout, H, W, x.device)
         nbytes = _ws_bytes("dd_conv_small_workspace_bytes", ks, cin, cout)
         ws = _ws(nbytes, x.device)
         sw = weight.stride()
@@ -421,7 +459,7 @@ class SmallConvFn(torch.autograd.Function):
         nbytes = _ws_bytes("dd_conv_small_workspace_bytes", ks, cin, cout)
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
-            gx = torch.empty((B, cin, H, W), dtype=torch.float32, device=g.device).as_strided((B, cin, H, W), (H * W * cin, 1, W * cin, cin))
+            gx = _nhwc_empty(B, cin, H, W, g.device)
             ws = _ws(nbytes, g.device)
             sw = weight.stride()
             L.check(lib.dd_conv_small_bwd_data(_p(g), _p(weight), sw[0], sw[1], sw[2], sw[3], B, H, W, cin, cout, ks, _p(gx), _p(ws), nbytes,
@@ -445,18 +483,14 @@ def mfma_conv_ok(x, weight, stride, padding, dilation, groups):
     tensor with enough pixels to fill the chip (csrc/dd_conv_mfma.hip: fp32 accuracy from three bf16 pieces per operand)."""
     if os.environ.get("DD_STOCK_MFMA_CONV", "0") == "1":
         return False
-    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4 and tuple(weight.shape[2:]) == (3, 3)):
+    if not (x.is_cuda and x.dtype == torch.float32 and weight.dtype == torch.float32 and x.dim() == 4):
+        return False
+    if not _conv3x3_s1(x, weight, stride, padding, dilation, groups, ((0, 0), (1, 1))) or torch.is_autocast_enabled():
         return False
     cout, cin = weight.shape[:2]
-    if groups != 1 or tuple(stride) != (1, 1) or tuple(dilation) != (1, 1) or tuple(padding) not in ((0, 0), (1, 1)) or x.shape[1] != cin:
-        return False
-    if torch.is_autocast_enabled():
-        return False
     pad = padding[0]
     Ho, Wo = x.shape[2] + 2 * pad - 2, x.shape[3] + 2 * pad - 2
-    # below ~20 k output pixels the 8 x 32-pixel tiles no longer fill the chip (12 x 24 x 80 is still ahead of the library on all three
-    # passes, 12 x 12 x 40 is not: profiles/r05_conv_mfma.txt)
-    if Ho < 8 or Wo < 32 or x.shape[0] * Ho * Wo < int(os.environ.get("DD_MFMA_CONV_MIN_PIXELS", "20000")):
+    if _below_tile_pixels(x.shape[0], Ho, Wo, "DD_MFMA_CONV_MIN_PIXELS"):
         # small images (the encoders' and decoders' deep levels): flat pixel tiles + split contraction, forward and data gradient
         return pad == 1 and _flat_conv_ok(x.shape[0], x.shape[2], x.shape[3], cin, cout)
     return bool(L.load().dd_conv3x3_mfma_supported(cin, cout))
@@ -474,7 +508,7 @@ def _flat_shape(B, H, W, pad, k_in=None, n_out=None):
     """Does MfmaConvFn take the flat-tile kernel for this input?  (the complement of the tile kernel's domain, see mfma_conv_ok;
     k_in / n_out: the channel counts of THIS pass -- the data gradient swaps them)"""
     Ho, Wo = H + 2 * pad - 2, W + 2 * pad - 2
-    if not (pad == 1 and (Ho < 8 or Wo < 32 or B * Ho * Wo < int(os.environ.get("DD_MFMA_CONV_MIN_PIXELS", "20000")))):
+    if not (pad == 1 and _below_tile_pixels(B, Ho, Wo, "DD_MFMA_CONV_MIN_PIXELS")):
         return False
     if os.environ.get("DD_FLAT_MFMA_CONV", "1") != "1":
         return False
@@ -501,138 +535,6 @@ def mfma_products():
     DD_MFMA_PRODUCTS overrides.  options.py: --matmul_precision."""
     env = os.environ.get("DD_MFMA_PRODUCTS")
     return int(env) if env else _PRODUCTS[torch.get_float32_matmul_precision()]
-
-
-def _nhwc_empty(B, Cc, H, W, device):
-    return torch.empty((B, H, W, Cc), dtype=torch.float32, device=device).permute(0, 3, 1, 2)
-
-
-class _PackEntry:
-    __slots__ = ("weight", "pack_f", "pack_b", "fresh", "sig")
-
-    def __init__(self, weight, pack_f, pack_b):
-        self.weight, self.pack_f, self.pack_b, self.fresh = weight, pack_f, pack_b, 0
-        self.sig = (weight.data_ptr(), tuple(weight.stride()), tuple(weight.shape))
-
-
-class PackSet:
-    """The dd_conv3x3_mfma weight packs of ONE network module, made by one launch at the top of its forward pass (round 6: the step had 62
-    pack launches of 4-8 us, each in front of its convolution on the network's stream; dd_conv3x3_mfma_pack_many makes a network's in one).
-    A layer joins the set the first time MfmaConvFn.forward runs inside the module's forward (it packs alone that time, its buffers become
-    the set's); from the next pass on the module's forward-pre hook packs every member and marks it fresh, the layer takes the fresh pack
-    ONCE -- any other call (outside the module's forward, a second use in one pass, a weight that moved) packs alone as before, so a pack
-    is never older than the forward pass that uses it.  Job tables and pack buffers are never freed: captured graphs hold their addresses."""
-
-    def __init__(self):
-        self.entries = {}          # id(weight) -> _PackEntry
-        self.tables = {}           # (with data-gradient packs?, members' signatures) -> (jobs, block_job, n_blocks)
-        self.retired = []          # buffers replaced by an upgrade (a member that later needed its data-gradient pack)
-
-    def pack_all(self):
-        if not self.entries:
-            return
-        with_b = torch.is_grad_enabled()
-        members = list(self.entries.values())
-        # a member whose weight moved (another device, another layout) leaves the set: its layer re-joins with the next call
-        for e in members:
-            if e.sig != (e.weight.data_ptr(), tuple(e.weight.stride()), tuple(e.weight.shape)):
-                self.retired.append(self.entries.pop(id(e.weight)))
-        members = list(self.entries.values())
-        if not members:
-            return
-        sig = tuple((e.sig, e.pack_f.data_ptr(), 0 if e.pack_b is None else e.pack_b.data_ptr()) for e in members)
-        table = self.tables.get((with_b, sig))
-        lib = L.load()
-        if table is None:
-            if torch.cuda.is_current_stream_capturing():
-                return             # no host-to-device copy inside a capture: this pass packs layer by layer
-            for mode in (True, False):          # both tables at once: a tape-free pass of the same members may first come inside a capture
-                self.tables[(mode, sig)] = self._table(lib, members, mode)
-            table = self.tables[(with_b, sig)]
-        L.check(lib.dd_conv3x3_mfma_pack_many(_p(table[0]), _p(table[1]), table[2], L.current_stream()), "dd_conv3x3_mfma_pack_many")
-        _PACK_MANY_LAUNCHES[0] += 1
-        for e in members:
-            e.fresh = 2 if (with_b and e.pack_b is not None) else 1
-
-    @staticmethod
-    def _table(lib, members, with_b):
-        words = lib.dd_conv3x3_mfma_pack_many_job_words()
-        jobs, owner, first = [], [], 0
-        for n, e in enumerate(members):
-            cout, cin = e.weight.shape[:2]
-            has_b = with_b and e.pack_b is not None
-            sw = e.weight.stride()
-            row = [e.weight.data_ptr(), sw[0], sw[1], sw[2], sw[3], cout, cin, e.pack_f.data_ptr(), e.pack_b.data_ptr() if has_b else 0, first]
-            assert len(row) == words
-            jobs.append(row)
-            nb = lib.dd_conv3x3_mfma_pack_many_blocks(cout, cin, 1, 1 if has_b else 0)
-            owner += [n] * nb
-            first += nb
-        dev = members[0].weight.device
-        return torch.tensor(jobs, dtype=torch.int64).to(dev), torch.tensor(owner, dtype=torch.int32).to(dev), first
-
-    def take(self, weight, need_b):
-        """The fresh pack of this weight, once: (pack_fwd, pack_bwd_data) or None."""
-        e = self.entries.get(id(weight))
-        if e is None or e.weight is not weight or e.fresh < (2 if need_b else 1):
-            return None
-        if e.sig != (weight.data_ptr(), tuple(weight.stride()), tuple(weight.shape)):
-            return None
-        e.fresh = 0
-        return e.pack_f, (e.pack_b if need_b else None)
-
-    def join(self, weight, pack_f, pack_b):
-        old = self.entries.get(id(weight))
-        if old is not None:
-            if old.weight is weight and old.sig == (weight.data_ptr(), tuple(weight.stride()), tuple(weight.shape)) and (pack_b is None or old.pack_b is not None):
-                return             # a second use in one pass, or a tape-free pass of a member: nothing to learn
-            self.retired.append(old)
-        self.entries[id(weight)] = _PackEntry(weight, pack_f, pack_b)
-
-    def end(self):
-        for e in self.entries.values():
-            e.fresh = 0
-
-
-_PACK_SETS = {}                # id(module) -> (weak reference to the module, PackSet)
-_ACTIVE_PACK_SETS = []         # the sets of the modules whose forward is running (innermost last)
-_PACK_MANY_LAUNCHES = [0]
-
-
-def pack_many_launches():
-    """How many times a network's packs were made by one dd_conv3x3_mfma_pack_many launch in this process."""
-    return _PACK_MANY_LAUNCHES[0]
-
-
-def _pack_many_on():
-    # OPT-IN: measured neutral in the headline step (341.7 / 341.3 img/s with it, 342.2 / 343.5 without, same box back to back) although it
-    # takes 54 launches and 0.32 ms of kernel time out of the step -- the packs were never on the step's critical path, and one 60 us
-    # launch at the head of an encoder delays its first convolution more than the 4-8 us packs interleaved with other streams' work did
-    return os.environ.get("DD_PACK_MANY", "0") == "1"
-
-
-def pack_weights_once_per_forward(module):
-    """Make `module` (a network: an encoder, a decoder) pack the weights of its dd_conv3x3_mfma layers in ONE launch at the top of every
-    forward pass (PackSet) when DD_PACK_MANY=1.  Returns the module.  Default (0): every layer packs in front of its own convolution."""
-    import weakref
-    if id(module) in _PACK_SETS and _PACK_SETS[id(module)][0]() is module:
-        return module
-    ps = PackSet()
-    _PACK_SETS[id(module)] = (weakref.ref(module, lambda _r, k=id(module): _PACK_SETS.pop(k, None)), ps)
-
-    def before(_m, _inputs):
-        _ACTIVE_PACK_SETS.append(ps)
-        if _pack_many_on():
-            ps.pack_all()
-
-    def after(_m, _inputs, _outputs):
-        ps.end()
-        if _ACTIVE_PACK_SETS and _ACTIVE_PACK_SETS[-1] is ps:
-            _ACTIVE_PACK_SETS.pop()
-
-    module.register_forward_pre_hook(before)
-    module.register_forward_hook(after, always_call=True)
-    return module
 
 
 class MfmaConvFn(torch.autograd.Function):
@@ -708,14 +610,9 @@ class MfmaConvFn(torch.autograd.Function):
                 L.check(lib.dd_conv3x3_mfma_bwd_weight_n(_p(x), _p(g), B, Hi, Wi, cin, cout, pad, products, _p(flat), _p(ws), nbytes, stream), "dd_conv3x3_mfma_bwd_weight")
                 gw = flat.view(cout, 3, 3, cin).permute(0, 3, 1, 2)           # (cout,cin,3,3) on channels-last memory
             else:
-                _, gw, _ = torch.ops.aten.convolution_backward(g, x, weight, None, (1, 1), (pad, pad), (1, 1), False, [0, 0], 1, (False, True, False))
+                gw = _wgrad_3x3_library(g, x, weight, pad)
         if has_bias and ctx.needs_input_grad[2]:
-            if cout <= 256:
-                gb = torch.empty(cout, dtype=torch.float32, device=g.device)
-                ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), g.device)
-                L.check(lib.dd_channel_sum_nhwc_t(_p(g), B * Ho * Wo, cout, _p(gb), DTYPE_CODE[g.dtype], _p(ws), stream), "dd_channel_sum_nhwc_t")
-            else:
-                gb = g.sum((0, 2, 3))
+            gb = _channel_sum(g, B * Ho * Wo, cout, DTYPE_CODE[g.dtype], stream) if cout <= 256 else g.sum((0, 2, 3))
         return gx, gw, gb, None
 
 
@@ -740,14 +637,14 @@ def half_conv_ok(x, weight, stride, padding, dilation, groups):
         return False
     if not torch.is_autocast_enabled() or torch.get_autocast_dtype("cuda") != x.dtype or weight.dtype not in (torch.float32, x.dtype):
         return False
+    if not _conv3x3_s1(x, weight, stride, padding, dilation, groups, ((0, 0), (1, 1))):
+        return False
+    if not (x.is_contiguous(memory_format=torch.channels_last) or x.stride(1) == 1):
+        return False
     cout, cin = weight.shape[:2]
-    if tuple(weight.shape[2:]) != (3, 3) or groups != 1 or tuple(stride) != (1, 1) or tuple(dilation) != (1, 1) or tuple(padding) not in ((0, 0), (1, 1)):
-        return False
-    if x.shape[1] != cin or not (x.is_contiguous(memory_format=torch.channels_last) or x.stride(1) == 1):
-        return False
     pad = padding[0]
     Ho, Wo = x.shape[2] + 2 * pad - 2, x.shape[3] + 2 * pad - 2
-    if Ho < 8 or Wo < 32 or x.shape[0] * Ho * Wo < int(os.environ.get("DD_HALF_CONV_MIN_PIXELS", "20000")):
+    if _below_tile_pixels(x.shape[0], Ho, Wo, "DD_HALF_CONV_MIN_PIXELS"):
         return False
     return bool(L.load().dd_conv3x3_half_supported(cin, cout))
 
@@ -773,7 +670,7 @@ class HalfConvFn(torch.autograd.Function):
         stream = L.current_stream()
         L.check(lib.dd_conv3x3_half_pack(_p(w32), sw[0], sw[1], sw[2], sw[3], cout, cin, code, _p(pack_f), _p(pack_b), stream), "dd_conv3x3_half_pack")
         Ho, Wo = Hi + 2 * pad - 2, Wi + 2 * pad - 2
-        y = torch.empty((B, Ho, Wo, cout), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
+        y = _nhwc_empty(B, cout, Ho, Wo, x.device, dtype=x.dtype)
         b32 = None if bias is None else (bias if bias.dtype == torch.float32 else bias.float())
         L.check(lib.dd_conv3x3_half(_p(x), _p(pack_f), _p(b32), B, Hi, Wi, cin, cout, pad, code, _p(y), stream), "dd_conv3x3_half")
         _HALF_CONV_CALLS[0] += 1
@@ -794,7 +691,7 @@ class HalfConvFn(torch.autograd.Function):
         gx = gw = gb = None
         stream = L.current_stream()
         if ctx.needs_input_grad[0]:
-            gx = torch.empty((B, Hi, Wi, cin), dtype=x.dtype, device=g.device).permute(0, 3, 1, 2)
+            gx = _nhwc_empty(B, cin, Hi, Wi, g.device, dtype=x.dtype)
             L.check(lib.dd_conv3x3_half(_p(g), _p(pack_b), None, B, Ho, Wo, cout, cin, 2 - pad, code, _p(gx), stream), "dd_conv3x3_half (data gradient)")
         if ctx.needs_input_grad[1]:
             if (min(cin, cout) >= 32 and weight.dtype == torch.float32 and os.environ.get("DD_STOCK_HALF_WGRAD", "0") != "1"
@@ -809,17 +706,10 @@ class HalfConvFn(torch.autograd.Function):
                 L.check(lib.dd_conv3x3_half_bwd_weight(_p(x), _p(g), B, Hi, Wi, cin, cout, pad, code, _p(flat), _p(ws), nbytes, stream), "dd_conv3x3_half_bwd_weight")
                 gw = flat.view(cout, 3, 3, cin).permute(0, 3, 1, 2)           # (cout,cin,3,3) on channels-last memory
             else:
-                # the library's half-precision weight gradient (only the shape, type and layout of the weight argument are read)
-                w_like = torch.empty_like(weight, dtype=x.dtype)
-                _, gw, _ = torch.ops.aten.convolution_backward(g, x, w_like, None, (1, 1), (pad, pad), (1, 1), False, [0, 0], 1, (False, True, False))
-                gw = gw.to(weight.dtype)
+                # the library's half-precision weight gradient
+                gw = _wgrad_3x3_library(g, x, torch.empty_like(weight, dtype=x.dtype), pad).to(weight.dtype)
         if has_bias and ctx.needs_input_grad[2]:
-            if cout <= 256:
-                gb = torch.empty(cout, dtype=torch.float32, device=g.device)
-                ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), g.device)
-                L.check(lib.dd_channel_sum_nhwc_t(_p(g), B * Ho * Wo, cout, _p(gb), code, _p(ws), stream), "dd_channel_sum_nhwc_t")
-            else:
-                gb = g.float().sum((0, 2, 3))
+            gb = _channel_sum(g, B * Ho * Wo, cout, code, stream) if cout <= 256 else g.float().sum((0, 2, 3))
             gb = gb.to(bias_dtype)
         return gx, gw, gb, None
 
@@ -894,7 +784,6 @@ def _nhwc(t):
 
 def up_cat_pad_ok(x, skip, mode):
     """Whether up_cat_pad() has its HIP path for these tensors (channels-last fp32 / fp16 / bf16 GPU tensors, channels in fours)."""
-    import os
     if os.environ.get("DD_STOCK_DECODER_GLUE", "0") == "1":
         return False
     if not (x.is_cuda and x.dtype in DTYPE_CODE and x.dim() == 4 and x.shape[1] % 4 == 0 and x.shape[1] >= 4 and _nhwc(x)
@@ -991,15 +880,9 @@ class PointwiseLinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             gx = torch.mm(g.view(-1, cout), weight).view(B, H, W, cin)
         if ctx.needs_input_grad[1]:
-            _, gw, _ = torch.ops.aten.convolution_backward(g.permute(0, 3, 1, 2), x.permute(0, 3, 1, 2), weight.view(cout, cin, 1, 1), None,
-                                                           [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])
-            gw = gw.reshape(cout, cin)
+            gw = _wgrad_1x1(g, x, weight, B, H, W)
         if ctx.needs_input_grad[2]:
-            lib = L.load()
-            gb = torch.empty(cout, dtype=torch.float32, device=g.device)
-            ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), g.device)
-            L.check(lib.dd_channel_sum_nhwc_t(_p(g), B * H * W, cout, _p(gb), DTYPE_CODE[g.dtype], _p(ws), L.current_stream()), "dd_channel_sum_nhwc_t")
-            gb = gb.to(weight.dtype)
+            gb = _channel_sum(g, B * H * W, cout, DTYPE_CODE[g.dtype], L.current_stream()).to(weight.dtype)
         return gx, gw, gb
 
 
@@ -1040,6 +923,17 @@ def mlp_ok(y, block):
                 and l1.bias is not None and l2.bias is not None and l1.in_features % 32 == 0 and l1.out_features % 32 == 0
                 and l2.in_features == l1.out_features and l2.out_features == l1.in_features and y.shape[-1] == l1.in_features
                 and isinstance(block.act, torch.nn.GELU) and getattr(block.act, "approximate", "none") == "none")
+
+
+def _mlp_param_grads(needs, g, gpre, y, post, w1, w2, B, H, W, stream):
+    """(gw1, gb1, gw2, gb2) of an MLP block once dd_gelu_pair has run, launched in that order, None where needs_input_grad does not ask.
+    g: the block's output gradient, gpre: the pre-activation's, post = GELU(pre), y: the block's input -- B*H*W rows each."""
+    M, code = B * H * W, DTYPE_CODE[torch.float32]
+    gw1 = _wgrad_1x1(gpre, y, w1, B, H, W) if needs[1] else None
+    gb1 = _channel_sum(gpre, M, w1.shape[0], code, stream) if needs[2] else None
+    gw2 = _wgrad_1x1(g, post, w2, B, H, W) if needs[3] else None
+    gb2 = _channel_sum(g, M, w2.shape[0], code, stream) if needs[4] else None
+    return gw1, gb1, gw2, gb2
 
 
 class MlpFn(torch.autograd.Function):
@@ -1087,32 +981,11 @@ class MlpFn(torch.autograd.Function):
         L.check(lib.dd_pw_gemm(_p(g), p0 + nb1 + nb2, None, M, Cc, hid, 0, _p(gpre), stream), "dd_pw_gemm (g . w2)")
         post = torch.empty((M, hid), dtype=torch.float32, device=g.device)
         L.check(lib.dd_gelu_pair(_p(pre), _p(gpre), _p(post), M * hid, stream), "dd_gelu_pair")
-        gy = gw1 = gb1 = gw2 = gb2 = None
+        gy = None
         if ctx.needs_input_grad[0]:
             gy = torch.empty((B, H, W, Cc), dtype=torch.float32, device=g.device)
             L.check(lib.dd_pw_gemm(_p(gpre), p0 + 2 * nb1 + nb2, None, M, hid, Cc, 0, _p(gy), stream), "dd_pw_gemm (g_pre . w1)")
-
-        def wgrad(go, x, w):                # (M,cout), (M,cin) -> (cout,cin): MIOpen's 1x1 weight gradient on channels-last views
-            cout, cin = w.shape
-            _, gw, _ = torch.ops.aten.convolution_backward(go.view(B, H, W, cout).permute(0, 3, 1, 2), x.view(B, H, W, cin).permute(0, 3, 1, 2),
-                                                           w.view(cout, cin, 1, 1), None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])
-            return gw.reshape(cout, cin)
-
-        def colsum(go, cout):
-            gb = torch.empty(cout, dtype=torch.float32, device=go.device)
-            ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), go.device)
-            L.check(lib.dd_channel_sum_nhwc_t(_p(go), M, cout, _p(gb), DTYPE_CODE[torch.float32], _p(ws), stream), "dd_channel_sum_nhwc_t")
-            return gb
-
-        if ctx.needs_input_grad[1]:
-            gw1 = wgrad(gpre, y, w1)
-        if ctx.needs_input_grad[2]:
-            gb1 = colsum(gpre, hid)
-        if ctx.needs_input_grad[3]:
-            gw2 = wgrad(g, post, w2)
-        if ctx.needs_input_grad[4]:
-            gb2 = colsum(g, Cc)
-        return gy, gw1, gb1, gw2, gb2
+        return (gy,) + _mlp_param_grads(ctx.needs_input_grad, g, gpre, y, post, w1, w2, B, H, W, stream)
 
 
 def mlp(y, block):
@@ -1127,11 +1000,8 @@ def mlp_fused_calls():
     return _MLP_FUSED_CALLS[0]
 
 
-def mlp_fused_ok(y, block):
-    """dd_mlp_fwd covers this block's pwconv2(GELU(pwconv1(y))) in ONE kernel: a pass that keeps nothing for a backward (the
-    statistics-only side batch, evaluation), fp32, C = 64 or 128, erf GELU, enough rows to fill the chip."""
-    if torch.is_grad_enabled() or os.environ.get("DD_STOCK_MLP_FUSED", "0") == "1" or torch.is_autocast_enabled():
-        return False
+def _mlp_block_ok(y, block):
+    """dd_mlp_fwd covers this block: fp32, contiguous (B,H,W,C) with enough rows to fill the chip, 6x expansion, erf GELU, C = 64 or 128."""
     l1, l2 = block.pwconv1, block.pwconv2
     if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and l1.weight.dtype == torch.float32):
         return False
@@ -1142,10 +1012,9 @@ def mlp_fused_ok(y, block):
                 and getattr(block.act, "approximate", "none") == "none" and L.load().dd_mlp_fwd_supported(l1.in_features))
 
 
-def mlp_fused(y, block):
-    """pwconv2(GELU(pwconv1(y))) through dd_mlp_fwd (csrc/dd_pw_gemm.hip: mlp_fwd_kernel): no tape, the hidden tensor never exists."""
+def _mlp_fwd_launch(y, w1, b1, w2, b2):
+    """pwconv2(GELU(pwconv1(y))) in one kernel: pack both weights (one launch), then dd_mlp_fwd; the hidden tensor never exists."""
     lib = L.load()
-    w1, b1, w2, b2 = block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias
     B, H, W, Cc = y.shape
     hid, M = w1.shape[0], B * H * W
     nb1, nb2 = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc), _ws_bytes("dd_pw_gemm_pack_bytes", Cc, hid)
@@ -1154,6 +1023,20 @@ def mlp_fused(y, block):
     L.check(lib.dd_mlp_pack(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, None, None, None, p0 + nb1, stream), "dd_mlp_pack")
     out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
     L.check(lib.dd_mlp_fwd(_p(y), p0, p0 + nb1, _p(b1), _p(b2), M, Cc, _p(out), stream), "dd_mlp_fwd")
+    return out
+
+
+def mlp_fused_ok(y, block):
+    """dd_mlp_fwd covers this block's pwconv2(GELU(pwconv1(y))) in ONE kernel: a pass that keeps nothing for a backward (the
+    statistics-only side batch, evaluation), fp32, C = 64 or 128, erf GELU, enough rows to fill the chip."""
+    if torch.is_grad_enabled() or os.environ.get("DD_STOCK_MLP_FUSED", "0") == "1" or torch.is_autocast_enabled():
+        return False
+    return _mlp_block_ok(y, block)
+
+
+def mlp_fused(y, block):
+    """pwconv2(GELU(pwconv1(y))) through dd_mlp_fwd (csrc/dd_pw_gemm.hip: mlp_fwd_kernel): no tape, the hidden tensor never exists."""
+    out = _mlp_fwd_launch(y, block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias)
     _MLP_FUSED_CALLS[0] += 1
     return out
 
@@ -1175,14 +1058,7 @@ def mlp_recompute_ok(y, block):
     between forward and backward."""
     if not torch.is_grad_enabled() or os.environ.get("DD_MLP_RECOMPUTE", "0") != "1" or torch.is_autocast_enabled():
         return False
-    l1, l2 = block.pwconv1, block.pwconv2
-    if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and l1.weight.dtype == torch.float32):
-        return False
-    if y.shape[0] * y.shape[1] * y.shape[2] < int(os.environ.get("DD_MLP_FUSED_MIN_ROWS", "16384")):
-        return False
-    return bool(l1.bias is not None and l2.bias is not None and l1.out_features == 6 * l1.in_features and l2.in_features == l1.out_features
-                and l2.out_features == l1.in_features and y.shape[-1] == l1.in_features and isinstance(block.act, torch.nn.GELU)
-                and getattr(block.act, "approximate", "none") == "none" and L.load().dd_mlp_fwd_supported(l1.in_features))
+    return _mlp_block_ok(y, block)
 
 
 class MlpRecomputeFn(torch.autograd.Function):
@@ -1196,15 +1072,7 @@ class MlpRecomputeFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, w1, b1, w2, b2):
-        lib = L.load()
-        B, H, W, Cc = y.shape
-        hid, M = w1.shape[0], B * H * W
-        nb1, nb2 = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc), _ws_bytes("dd_pw_gemm_pack_bytes", Cc, hid)
-        packs = torch.empty((nb1 + nb2) // 4, dtype=torch.float32, device=y.device)
-        p0, stream = packs.data_ptr(), L.current_stream()
-        L.check(lib.dd_mlp_pack(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, None, None, None, p0 + nb1, stream), "dd_mlp_pack")
-        out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
-        L.check(lib.dd_mlp_fwd(_p(y), p0, p0 + nb1, _p(b1), _p(b2), M, Cc, _p(out), stream), "dd_mlp_fwd")
+        out = _mlp_fwd_launch(y, w1, b1, w2, b2)
         _MLP_RECOMPUTE_CALLS[0] += 1
         ctx.save_for_backward(y, w1, b1, w2)
         return out
@@ -1223,32 +1091,11 @@ class MlpRecomputeFn(torch.autograd.Function):
             gpre = torch.mm(g2, w2)                             # g . w2 (M, 6C)
         post = torch.empty_like(pre)
         L.check(lib.dd_gelu_pair(_p(pre), _p(gpre), _p(post), M * hid, stream), "dd_gelu_pair")       # post = GELU(pre), gpre *= GELU'(pre)
-        gy = gw1 = gb1 = gw2 = gb2 = None
+        gy = None
         if ctx.needs_input_grad[0]:
             with torch.autocast("cuda", enabled=False):
                 gy = torch.mm(gpre, w1).view(B, H, W, Cc)
-
-        def wgrad(go, x, w):                # (M,cout), (M,cin) -> (cout,cin): MIOpen's 1x1 weight gradient on channels-last views
-            cout, cin = w.shape
-            _, gw, _ = torch.ops.aten.convolution_backward(go.view(B, H, W, cout).permute(0, 3, 1, 2), x.view(B, H, W, cin).permute(0, 3, 1, 2),
-                                                           w.view(cout, cin, 1, 1), None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1, [False, True, False])
-            return gw.reshape(cout, cin)
-
-        def colsum(go, cout):
-            gb = torch.empty(cout, dtype=torch.float32, device=go.device)
-            ws = _ws(_ws_bytes("dd_channel_sum_workspace_bytes", cout), go.device)
-            L.check(lib.dd_channel_sum_nhwc_t(_p(go), M, cout, _p(gb), DTYPE_CODE[torch.float32], _p(ws), stream), "dd_channel_sum_nhwc_t")
-            return gb
-
-        if ctx.needs_input_grad[1]:
-            gw1 = wgrad(gpre, y2, w1)
-        if ctx.needs_input_grad[2]:
-            gb1 = colsum(gpre, hid)
-        if ctx.needs_input_grad[3]:
-            gw2 = wgrad(g2, post, w2)
-        if ctx.needs_input_grad[4]:
-            gb2 = colsum(g2, Cc)
-        return gy, gw1, gb1, gw2, gb2
+        return (gy,) + _mlp_param_grads(ctx.needs_input_grad, g2, gpre, y2, post, w1, w2, B, H, W, stream)
 
 
 def mlp_recompute(y, block):

@@ -49,25 +49,33 @@ def transformation_from_parameters(axisangle, translation, invert=False):
     return torch.matmul(get_translation_matrix(translation), R)
 
 
+def _hip_conv(x, weight, bias, stride, padding, dilation, groups):
+    """A zero-padded conv2d on a GPU tensor through the first HIP path that covers it, or None: the caller takes the stock operator."""
+    if not x.is_cuda:
+        return None
+    from hipops.functions import ConvBiasFn, HeadConvFn, half_conv, half_conv_ok, head_conv_ok, mfma_conv, mfma_conv_ok, small_conv, small_conv_ok
+    conf = (stride, padding, dilation, groups)
+    if x.dtype != torch.float32 and half_conv_ok(x, weight, *conf):
+        return half_conv(x, weight, bias, padding[0])       # a half-precision network's 3x3, stride 1: csrc/dd_conv_half.hip
+    if small_conv_ok(x, weight, *conf):
+        return small_conv(x, weight, bias)                  # a handful of channels at full resolution: csrc/dd_conv_small.hip
+    if mfma_conv_ok(x, weight, *conf):
+        return mfma_conv(x, weight, bias, padding[0])       # 16+ channels, 3x3, stride 1: csrc/dd_conv_mfma.hip
+    if head_conv_ok(x, weight, *conf):
+        return HeadConvFn.apply(x, weight, bias)            # a disparity head (C -> 1): csrc/dd_conv_head.hip
+    if bias is not None and torch.is_grad_enabled() and os.environ.get("DD_STOCK_CONV_BIAS_GRAD", "0") != "1":
+        return ConvBiasFn.apply(x, weight, bias, *conf)     # the library's convolution, the bias gradient by the HIP channel sum
+    return None
+
+
 class Conv2d(nn.Conv2d):
-    """nn.Conv2d (same parameters / state_dict keys) whose bias gradient goes through the HIP channel-sum kernel on the
-    GPU -- see hipops.functions.ConvBiasFn.  CPU tensors and bias-free convs take the stock path."""
+    """nn.Conv2d (same parameters / state_dict keys) through _hip_conv; CPU tensors and other padding modes take the stock path."""
 
     def forward(self, x):
-        if x.is_cuda and self.padding_mode == "zeros":
-            from hipops.functions import HeadConvFn, half_conv, half_conv_ok, head_conv_ok, mfma_conv, mfma_conv_ok, small_conv, small_conv_ok
-            if x.dtype != torch.float32 and half_conv_ok(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-                return half_conv(x, self.weight, self.bias, self.padding[0])      # a half-precision network's 3x3, stride 1: csrc/dd_conv_half.hip
-            if small_conv_ok(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-                return small_conv(x, self.weight, self.bias)          # a handful of channels at full resolution: csrc/dd_conv_small.hip
-            if mfma_conv_ok(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-                return mfma_conv(x, self.weight, self.bias, self.padding[0])      # 16+ channels, 3x3, stride 1: csrc/dd_conv_mfma.hip
-            if head_conv_ok(x, self.weight, self.stride, self.padding, self.dilation, self.groups):
-                return HeadConvFn.apply(x, self.weight, self.bias)    # a disparity head (C -> 1): csrc/dd_conv_head.hip
-        if (self.bias is not None and x.is_cuda and self.padding_mode == "zeros" and torch.is_grad_enabled()
-                and os.environ.get("DD_STOCK_CONV_BIAS_GRAD", "0") != "1"):
-            from hipops.functions import ConvBiasFn
-            return ConvBiasFn.apply(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
+        if self.padding_mode == "zeros":
+            y = _hip_conv(x, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups)
+            if y is not None:
+                return y
         return super().forward(x)
 
 
@@ -117,16 +125,12 @@ def conv_cat_aligned(conv, parts, force=False):
         parts = [_as_channels_last(p) for p in parts]
     x = torch.cat(list(parts) + [zeros], 1)
     w = F.pad(conv.weight, (0, 0, 0, 0, 0, pad))
-    if x.is_cuda:
-        from hipops.functions import half_conv, half_conv_ok, mfma_conv, mfma_conv_ok
-        if x.dtype != torch.float32 and half_conv_ok(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
-            return half_conv(x, w, conv.bias, conv.padding[0])
-        if mfma_conv_ok(x, w, conv.stride, conv.padding, conv.dilation, conv.groups):
-            return mfma_conv(x, w, conv.bias, conv.padding[0])
-    if conv.bias is not None and x.is_cuda and torch.is_grad_enabled() and os.environ.get("DD_STOCK_CONV_BIAS_GRAD", "0") != "1":
-        from hipops.functions import ConvBiasFn
-        return ConvBiasFn.apply(x, w, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
-    return F.conv2d(x, w, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
+    # Of _hip_conv's chain only the half, mfma and ConvBiasFn links can match here: dd_conv_small takes at most 16 input channels and x
+    # has more than 32; dd_conv_head takes one output channel and no padding, and the callers are the motion decoders'
+    # refine_motion_conv*[0] (ch + out_dim -> ch channels, padding 1) and LiteMono's stem2 and downsample_layers[1:] (64 / 128 / 224
+    # output channels, padding 1).
+    y = _hip_conv(x, w, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
+    return y if y is not None else F.conv2d(x, w, conv.bias, conv.stride, conv.padding, conv.dilation, conv.groups)
 
 
 class DeferredStats:
