@@ -1,7 +1,9 @@
 // dd_reg.hip -- regularisers of Trainer.compute_losses on the low-res network outputs (gfx950):
-//   dd_smooth_loss    edge-aware smoothness, value + gradient in one pass   (tools.py:311-326, Trainer.py:355-359,380-381,401-402)
-//   dd_sparsity_loss  masked BCE-with-logits of the motion probability       (Trainer.py:393-399)
-//   dd_ground_loss    RANSAC ground plane + above-ground hinge               (tools.py:76-164, Trainer.py:361-364,425-461)
+//   smoothness  edge-aware, value + gradient in one pass                (tools.py:311-326, Trainer.py:355-359,380-381,401-402)
+//   sparsity    masked BCE-with-logits of the motion probability        (Trainer.py:393-399)
+//   ground      RANSAC ground plane + above-ground hinge                (tools.py:76-164, Trainer.py:361-364,425-461)
+// as per-term entry points (dd_smooth_loss, dd_ground_*), as the staged pipeline of dd_reg_losses_finish, and as the passes of
+// dd_fused_loss behind the photometric tile kernel.
 // All three are HBM-bound streaming kernels over (B,C,h,w) tensors: coalesced row-major reads, neighbours
 // come from L1/L2, per-block partial sums go through wave64 shuffles and are folded in a fixed order
 // (no float atomics on the loss values).  No host synchronisation anywhere -- the reference needs three
@@ -40,31 +42,14 @@ __device__ __forceinline__ float wsum_dpp(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-template <int NV, int NTHREADS>
-__device__ __forceinline__ float block_sum_dpp(float (&v)[NV], float* red /* NV * NTHREADS/64 */) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-    const float r = wsum_dpp(v[k]);
-    if (lane == 0) red[wave * NV + k] = r;
-  }
-  __syncthreads();
-  float out = 0.f;
-  if (threadIdx.x < NV) {
-#pragma unroll
-    for (int wv = 0; wv < NTHREADS / 64; ++wv) out += red[wv * NV + threadIdx.x];
-  }
-  __syncthreads();
-  return out;
-}
-
-// block-wide sum of up to NV values per thread; result valid in thread 0..NV-1 (value k in thread k)
-template <int NV, int NTHREADS>
+// block-wide sum of up to NV values per thread; result valid in thread 0..NV-1 (value k in thread k).  WAVE_SUM fixes the association
+// inside a wave: wsum, or wsum_dpp for the tasks that reduce many values per workgroup.
+template <int NV, int NTHREADS, float (*WAVE_SUM)(float) = wsum>
 __device__ __forceinline__ float block_sum(float (&v)[NV], float* red /* NV * NTHREADS/64 */) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
-    const float r = wsum(v[k]);
+    const float r = WAVE_SUM(v[k]);
     if (lane == 0) red[wave * NV + k] = r;
   }
   __syncthreads();
@@ -249,13 +234,7 @@ __device__ __forceinline__ void sparsity_count_body(int bx, int by, int gx, cons
   if (threadIdx.x < 2) partials[((size_t)b * SP_BPI + bx) * 2 + threadIdx.x] = r;
 }
 
-__global__ __launch_bounds__(SP_NT) void sparsity_count_kernel(const float* __restrict__ delta, const float* __restrict__ delta_sum,
-                                                                const float* __restrict__ prob, int n, float inv_total,
-                                                                float* __restrict__ partials) {
-  sparsity_count_body(blockIdx.x, blockIdx.y, gridDim.x, delta, delta_sum, prob, n, inv_total, partials);
-}
-
-template <int PXT = 1>
+template <int PXT>
 __device__ __forceinline__ void sparsity_grad_body(int bx, int by, int gx, const float* __restrict__ delta, const float* __restrict__ delta_sum,
                                                                const float* __restrict__ prob, int B, int n, float inv_total,
                                                                float weight, const float* __restrict__ partials,
@@ -305,19 +284,12 @@ __device__ __forceinline__ void sparsity_grad_body(int bx, int by, int gx, const
   }
 }
 
-__global__ __launch_bounds__(SP_NT) void sparsity_grad_kernel(const float* __restrict__ delta, const float* __restrict__ delta_sum,
-                                                               const float* __restrict__ prob, int B, int n, float inv_total,
-                                                               float weight, const float* __restrict__ partials,
-                                                               float* __restrict__ g_prob, float* __restrict__ out) {
-  sparsity_grad_body(blockIdx.x, blockIdx.y, gridDim.x, delta, delta_sum, prob, B, n, inv_total, weight, partials, g_prob, out);
-}
-
 // =================================================================================================
 // ground plane
 // =================================================================================================
 constexpr int GP_NT = 256;
 constexpr int GP_MAX_IT = 128;
-static_assert(GP_NT == 2 * GP_MAX_IT, "ground_count_body splits the workgroup into two halves of GP_MAX_IT candidates");
+static_assert(GP_NT == 2 * GP_MAX_IT, "disp_pre_body and image_fold_body split the workgroup into two halves of GP_MAX_IT candidates");
 
 // one thread per RANSAC candidate: least squares y = w1*x + w2*z + w3 through np points (tools.py:141-154),
 // (AtA + 1e-6 on EVERY entry)^-1 At B, solved in double to stay clear of the conditioning of 5 nearby points
@@ -345,69 +317,16 @@ __global__ __launch_bounds__(GP_NT) void ground_candidates_kernel(const float* _
 // scores every candidate against the ground points of ONE image.  The reference pairs candidate
 // j = b*max_it + it with the points of image (j mod B) -- `points.repeat(max_it,1,1)` at tools.py:130 tiles
 // the batch while the candidates are image-major -- and that pairing is reproduced here.
-// `part` == nullptr (per-term entry points): one point per thread, counts[] (zeroed) collects the inliers with atomics.
-// `part` != nullptr (dd_reg_losses): the workgroup covers GS_SLABS * GP_NT points and leaves its max_it inlier counts as one
-// record part[(img * gx + bx) * max_it + k] (plain stores; ground_count_body adds the records up).  The candidate planes
-// sit in the lanes of each wave and are broadcast with v_readlane, a thread keeps GS_SLABS points in registers, and lane k
-// accumulates the wave's count for candidates k and k + 64: no memory traffic and no atomics inside the loop.
-constexpr int GS_SLABS = 4;
+// One point per thread, counts[] (zeroed) collects the inliers with atomics (the per-term entry points).
 __device__ __forceinline__ void ground_score_body(int bx, int by, int gx, const float* __restrict__ disp, const float* __restrict__ inv_K,
                                                               const float* __restrict__ cand, int B, int h, int w, int rows,
                                                               int max_it, float tol, DepthParams dp,
-                                                              int* __restrict__ counts /* (B*max_it) zeroed */, int* __restrict__ part = nullptr) {
+                                                              int* __restrict__ counts /* (B*max_it) zeroed */) {
   const int img = by;
   const int n = h * w, base = (h - rows) * w, ng = rows * w;
   const int lane = threadIdx.x & 63;
   const float* disp_b = disp + (size_t)img * n * (inv_K ? 1 : 3);
   const float* invK_b = inv_K ? inv_K + img * 16 : nullptr;
-  if (part) {
-    __shared__ int s_wave[GP_NT / 64][GP_MAX_IT];
-    float P[GS_SLABS][3];
-#pragma unroll
-    for (int sl = 0; sl < GS_SLABS; ++sl) {
-      const int q = (bx * GS_SLABS + sl) * GP_NT + threadIdx.x;
-      P[sl][0] = 0.f; P[sl][1] = 3e38f; P[sl][2] = 0.f;            // a point beyond the data: |distance| is huge for every plane
-      if (q < ng) ground_point(disp_b, invK_b, dp, w, base + q, P[sl], n);
-    }
-    // lane k holds the planes of candidates k and k + 64; the loop broadcasts them with v_readlane (k is wave-uniform)
-    float pl[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int k = lane + 64 * hf;
-      if (k < max_it) {
-        const float* c = cand + (size_t)(img + k * B) * 3;
-        pl[hf][0] = c[0]; pl[hf][1] = c[1]; pl[hf][2] = c[2];
-      }
-    }
-    auto bcast = [](float v, int k) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k)); };
-    int cnt[2] = {0, 0};             // inliers of candidate `lane` / `lane + 64` seen by this wave
-#pragma unroll
-    for (int hf = 0; hf < 2; ++hf) {
-      const int kn = min(max_it - 64 * hf, 64);
-      for (int k = 0; k < kn; ++k) {
-        const float c0 = bcast(pl[hf][0], k), c1 = bcast(pl[hf][1], k), c2 = bcast(pl[hf][2], k);
-        int tot = 0;
-#pragma unroll
-        for (int sl = 0; sl < GS_SLABS; ++sl) {
-          const float dist = P[sl][0] * c0 + P[sl][2] * c1 + c2 - P[sl][1];
-          tot += __popcll(__ballot(dd_abs(dist) < tol));
-        }
-        if (lane == k) cnt[hf] += tot;
-      }
-    }
-    const int lo = cnt[0], hi = cnt[1];
-    const int wave = threadIdx.x >> 6;
-    s_wave[wave][lane] = lo;
-    s_wave[wave][lane + 64] = hi;
-    __syncthreads();
-    for (int k = threadIdx.x; k < max_it; k += GP_NT) {
-      int t = 0;
-#pragma unroll
-      for (int wv = 0; wv < GP_NT / 64; ++wv) t += s_wave[wv][k];
-      part[((size_t)img * gx + bx) * max_it + k] = t;
-    }
-    return;
-  }
   __shared__ float s_c[GP_MAX_IT * 3];
   __shared__ int s_j[GP_MAX_IT];
   __shared__ int s_cnt[GP_MAX_IT];
@@ -436,40 +355,24 @@ __device__ __forceinline__ void ground_score_body(int bx, int by, int gx, const 
     if (s_cnt[k]) atomicAdd(&counts[s_j[k]], s_cnt[k]);
 }
 
-// The same scoring on the matrix pipe (dd_reg_losses): distances of N points to max_it planes are a (N x 4)(4 x max_it) product --
-// rows [x, z, 1, -y], columns [w1, w2, w3, 1] -- and that, unlike the 3x3 window sums of the photometric kernel, IS a dense product:
-// two v_mfma_f32_32x32x2_f32 per 32 points x 32 candidates (exact fp32 products, fp32 accumulation), then |d| < tol as a compare +
-// add-with-carry per value.  Lane l supplies point l % 32 (both halves of the wave compute the same 32 points; k = l / 32 selects the
-// coordinate) and candidate column l % 32; its 16 results are 16 points of ONE candidate column, so a lane counts in registers and
-// the two halves meet once at the end.  0.25 cycles per (point, candidate) against ~0.8 for the readlane / ballot form above, which
-// made this task the second largest of the regularisers (24 us; scripts/reg_task_costs.sh).  Same records as ground_score_body.
+// The same scoring on the matrix pipe (dd_reg_losses_finish, dd_fused_loss): distances of N points to max_it planes are a
+// (N x 4)(4 x max_it) product -- rows [x, z, 1, -y], columns [w1, w2, w3, 1] -- and that, unlike the 3x3 window sums of the photometric
+// kernel, IS a dense product: two v_mfma_f32_32x32x2_f32 per 32 points x 32 candidates (exact fp32 products, fp32 accumulation), then
+// |d| < tol as a compare + add-with-carry per value.  Lane l supplies point l % 32 (both halves of the wave compute the same 32 points;
+// k = l / 32 selects the coordinate) and candidate column l % 32; its 16 results are 16 points of ONE candidate column, so a lane
+// counts in registers and the two halves meet once at the end: 0.25 cycles per (point, candidate), against ~0.8 for a VALU form with
+// v_readlane broadcasts and ballots.  The workgroup covers GS_SLABS * GP_NT points and leaves its max_it inlier counts as one record
+// part[(img * gx + bx) * max_it + k] (plain stores, no atomics; disp_pre_body / image_fold_body add the records up).
+constexpr int GS_SLABS = 4;
 typedef float gs_f16v __attribute__((ext_vector_type(16)));
-// rand_idx != nullptr (dd_fused_loss): the workgroup first SOLVES the max_it candidates it scores (candidate img + k*B, thread k; five
-// gathered points and a 3x3 solve in fp64 each -- identical arithmetic in every workgroup, hence identical planes) instead of reading
-// them from a launch in front of this one; workgroup 0 of an image also publishes them in `cand_out` for the winner's look-up.
 __device__ __forceinline__ void ground_score_mfma_body(int bx, int img, int gx, const float* __restrict__ disp, const float* __restrict__ inv_K,
                                                        const float* __restrict__ cand, int B, int h, int w, int rows, int max_it, float tol,
-                                                       DepthParams dp, int* __restrict__ part, const int32_t* __restrict__ rand_idx = nullptr,
-                                                       int np = 0, float* __restrict__ cand_out = nullptr) {
+                                                       DepthParams dp, int* __restrict__ part) {
   __shared__ int s_wave[GP_NT / 64][GP_MAX_IT];
-  __shared__ float s_cand[GP_MAX_IT * 3];
   const int n = h * w, base = (h - rows) * w, ng = rows * w;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, hi = lane >> 5;
   const float* disp_b = disp + (size_t)img * n;
   const float* invK_b = inv_K + img * 16;
-  if (rand_idx) {             // uniform
-    if ((int)threadIdx.x < max_it) {
-      const int jc = img + (int)threadIdx.x * B;
-      float cv[3];
-      ground_candidate_solve(disp, inv_K, rand_idx, B, h, w, rows, np, max_it, dp, jc, cv);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        s_cand[threadIdx.x * 3 + i] = cv[i];
-        if (bx == 0 && cand_out) cand_out[(size_t)jc * 3 + i] = cv[i];
-      }
-    }
-    __syncthreads();
-  }
   // candidate columns: tile t holds candidates t*32 .. t*32+31 (of the max_it scored on this image: j' = img + k*B, tools.py:130)
   float b1[4], b2[4];
 #pragma unroll
@@ -477,11 +380,8 @@ __device__ __forceinline__ void ground_score_mfma_body(int bx, int img, int gx, 
     const int k = t * 32 + j;
     float c0 = 0.f, c1 = 0.f, c2 = 3e38f;               // a padding column: every distance huge
     if (k < max_it) {
-      if (rand_idx) { c0 = s_cand[k * 3]; c1 = s_cand[k * 3 + 1]; c2 = s_cand[k * 3 + 2]; }
-      else {
-        const float* c = cand + (size_t)(img + k * B) * 3;
-        c0 = c[0]; c1 = c[1]; c2 = c[2];
-      }
+      const float* c = cand + (size_t)(img + k * B) * 3;
+      c0 = c[0]; c1 = c[1]; c2 = c[2];
     }
     b1[t] = hi ? c1 : c0;           // k = 0: w1, k = 1: w2      (pairs with [x, z])
     b2[t] = hi ? 1.f : c2;          // k = 0: w3, k = 1: 1       (pairs with [1, -y])
@@ -527,8 +427,8 @@ __device__ __forceinline__ void ground_score_mfma_body(int bx, int img, int gx, 
   }
 }
 
-// ... as a kernel of its own, one launch for all scales (between stage 1 and stage 2): the 64 accumulator registers of four candidate
-// tiles would otherwise set the occupancy of every task of reg_stage_kernel (95 -> 128+ VGPRs).
+// ... in the staged pipeline as a kernel of its own, one launch for all scales (between stage 1 and stage 2): the 64 accumulator
+// registers of four candidate tiles would otherwise set the occupancy of every task of reg_stage_kernel (95 -> 128+ VGPRs).
 struct ScoreScale {
   const float* disp;
   const float* inv_K;
@@ -555,21 +455,6 @@ __global__ __launch_bounds__(GP_NT) void ground_score_all_kernel(const ScoreArgs
 #undef DD_GS_SCALE
     default: break;
   }
-}
-
-// counts[img + k*B] = sum over the gx records of image img (the pairing of ground_score_body), one workgroup per image:
-// thread (k, half) adds every second record, the two halves meet in LDS.  Integer sums: any order gives the same result.
-__device__ __forceinline__ void ground_count_body(int by, int gx, const int* __restrict__ part, int B, int max_it, int* __restrict__ counts) {
-  __shared__ int s_half[GP_MAX_IT];
-  const int img = by, k = threadIdx.x & (GP_MAX_IT - 1), half = threadIdx.x / GP_MAX_IT;     // GP_NT == 2 * GP_MAX_IT
-  int acc = 0;
-  if (k < max_it) {
-#pragma unroll 8
-    for (int r = half; r < gx; r += 2) acc += part[((size_t)img * gx + r) * max_it + k];
-  }
-  if (half == 1) s_half[k] = acc;
-  __syncthreads();
-  if (half == 0 && k < max_it) counts[img + k * B] = acc + s_half[k];
 }
 
 __global__ __launch_bounds__(GP_NT) void ground_score_kernel(const float* __restrict__ disp, const float* __restrict__ inv_K,
@@ -713,7 +598,7 @@ __global__ __launch_bounds__(64) void assemble_kernel(const float* __restrict__ 
   }
 }
 
-// dd_reg_losses_finish: stage 5 and the assembling in ONE workgroup -- the hinge partials of every scale are folded in a fixed
+// dd_reg_losses_finish: the hinge fold and the assembling in ONE workgroup -- the hinge partials of every scale are folded in a fixed
 // order into their res slot, then the same arithmetic as assemble_kernel.
 struct HingeFold {
   const float* part[DD_MAX_SCALES];     // per-workgroup hinge sums of the scale (nullptr: no ground term)
@@ -862,7 +747,7 @@ __global__ __launch_bounds__(256) void fused_finish_kernel(float* __restrict__ r
 }
 
 // =================================================================================================
-// smoothness of ALL entries of a scale in one pass (dd_reg_losses)
+// smoothness of ALL entries of a scale in one pass (dd_reg_losses_finish)
 // =================================================================================================
 // One thread per low-res pixel of one image handles every smoothed channel of the scale (disparity | flow x 3 | mask, or the
 // per-frame variants): the colour neighbourhood is loaded once and the four edge weights exp(-mean_c |dI|) are formed once for
@@ -872,7 +757,7 @@ __global__ __launch_bounds__(256) void fused_finish_kernel(float* __restrict__ r
 // Entry layout: DDRegScale.smooth[k], k in ascending order; channel ch of the scale = (entry, channel) in that order.
 constexpr int SMA_MAX_ENTRIES = DD_REG_SMOOTH;
 constexpr int SMA_MAX_CH = 9;
-// Pixels per thread of the element-wise tasks of dd_reg_losses.  The tasks are bound by the number of workgroups, not by bytes:
+// Pixels per thread of the element-wise tasks of the staged pipeline.  The tasks are bound by the number of workgroups, not by bytes:
 // a workgroup spends most of its life in its prologue / epilogue (fold of per-image records, barriers, a 15-value block
 // reduction) -- at one pixel per thread the stage kernels retired ~160 workgroups per microsecond whatever they carried
 // (23 000 workgroups = 149 us in stage 2).  More pixels per workgroup amortise that part.
@@ -963,8 +848,6 @@ __device__ __forceinline__ void smooth_all_body(int bx, int b, int gx, const DDR
     float e_r = 0.f, e_l = 0.f, e_d = 0.f, e_u = 0.f;
 #pragma unroll
     for (int c0 = 0; c0 < NCH; c0 += GROUP) {
-      constexpr int dummy = 0;
-      (void)dummy;
       float a_c[GROUP], a_r[GROUP], a_l[GROUP], a_d[GROUP], a_u[GROUP], g_old[GROUP];
 #pragma unroll
       for (int j = 0; j < GROUP; ++j) {
@@ -1140,7 +1023,7 @@ __device__ __forceinline__ void smooth_quad_body(int bx, int b, const SmoothQuad
       }
     }
   }
-  const float r = block_sum_dpp<3 * SMA_MAX_ENTRIES, SM_NT>(acc, red);
+  const float r = block_sum<3 * SMA_MAX_ENTRIES, SM_NT, wsum_dpp>(acc, red);
 #pragma unroll
   for (int e = 0; e < SMA_MAX_ENTRIES; ++e) {
     const int j = (int)threadIdx.x - 3 * e;
@@ -1445,7 +1328,7 @@ __device__ __forceinline__ void combine_smooth_body(int bx, int b, const Combine
       }
     }
   }
-  const float r = block_sum_dpp<NSMOOTH, SM_NT>(acc, red);
+  const float r = block_sum<NSMOOTH, SM_NT, wsum_dpp>(acc, red);
   if ((int)threadIdx.x < NSMOOTH) q.part[((size_t)b * gx + bx) * 8 + threadIdx.x] = r;
 }
 
@@ -1504,28 +1387,14 @@ __device__ __forceinline__ void tile_fold_body(int vb, const TileFoldArgs& f) {
 }
 
 // second launch of dd_fused_loss.  Task ranges: footprint sums + smoothness (scales >= 1; memory-bound) | tile-record fold |
-// candidate scoring (all scales; matrix pipe + VALU) | per-image disparity sums.  The memory-bound workgroups are dispatched FIRST:
-// with the scoring in front its ~750 workgroups took every slot of the chip and the rest of the launch ran behind them (38 us for
-// 19 + 11 + 7 us of tasks).
-struct PostScore {
-  ScoreScale sc[DD_MAX_SCALES];
-  const int32_t* rand_idx[DD_MAX_SCALES];
-  float* cand_out[DD_MAX_SCALES];
-  int num_scales, B, max_it, np;
-  float tol;
-  DepthParams dp;
-};
-struct PostMean {
-  const float* inp[DD_MAX_SCALES];   // the scale's disparity (nullptr: no mean needed)
-  float* partial[DD_MAX_SCALES];
-  int n[DD_MAX_SCALES], first[DD_MAX_SCALES];
-};
+// candidate scoring (all scales; matrix pipe + VALU; the planes come from the tile kernel's side workgroups).  The memory-bound
+// workgroups are dispatched FIRST: with the scoring in front its ~750 workgroups took every slot of the chip and the rest of the launch
+// ran behind them (38 us for 19 + 11 + 7 us of tasks).
 struct PostArgs {
-  PostScore score;
+  ScoreArgs score;
   CombineArgs comb;
   TileFoldArgs fold;
-  PostMean mean;
-  int num_scales, first_fold, first_score, first_mean;      // combine tasks start at workgroup 0
+  int num_scales, first_fold, first_score;      // combine tasks start at workgroup 0, scoring tasks run to the end of the grid
 };
 
 template <int NCH>
@@ -1547,7 +1416,7 @@ __global__ __launch_bounds__(RT_NT_FUSED) void fused_post_kernel(const PostArgs 
     }
   } else if (blk < a.first_score) {
     tile_fold_body(blk - a.first_fold, a.fold);
-  } else if (blk < a.first_mean) {
+  } else {
     const int sb = blk - a.first_score;
     int si = 0;
 #pragma unroll
@@ -1556,23 +1425,9 @@ __global__ __launch_bounds__(RT_NT_FUSED) void fused_post_kernel(const PostArgs 
     switch (si) {       // constant offsets into the kernel-argument block
 #define DD_PS_SCALE(I) case I: { const int vb = sb - a.score.sc[I].first; \
       if (a.score.sc[I].gx > 0) ground_score_mfma_body(vb % a.score.sc[I].gx, vb / a.score.sc[I].gx, a.score.sc[I].gx, a.score.sc[I].disp, a.score.sc[I].inv_K, a.score.sc[I].cand, a.score.B, \
-                             a.score.sc[I].h, a.score.sc[I].w, a.score.sc[I].rows, a.score.max_it, a.score.tol, a.score.dp, a.score.sc[I].part, \
-                             a.score.rand_idx[I], a.score.np, a.score.cand_out[I]); break; }
+                             a.score.sc[I].h, a.score.sc[I].w, a.score.sc[I].rows, a.score.max_it, a.score.tol, a.score.dp, a.score.sc[I].part); break; }
       DD_PS_SCALE(0) DD_PS_SCALE(1) DD_PS_SCALE(2) DD_PS_SCALE(3)
 #undef DD_PS_SCALE
-      default: break;
-    }
-  } else {
-    const int mb = blk - a.first_mean;
-    int si = 0;
-#pragma unroll
-    for (int i = 1; i < DD_MAX_SCALES; ++i)
-      if (i < a.num_scales && a.mean.inp[i] && mb >= a.mean.first[i]) si = i;
-    switch (si) {
-#define DD_PM_SCALE(I) case I: { const int vb = mb - a.mean.first[I]; \
-      if (a.mean.inp[I]) plane_sum_body(vb % MEAN_BPI, vb / MEAN_BPI, MEAN_BPI, a.mean.inp[I], a.mean.n[I], a.mean.partial[I]); break; }
-      DD_PM_SCALE(0) DD_PM_SCALE(1) DD_PM_SCALE(2) DD_PM_SCALE(3)
-#undef DD_PM_SCALE
       default: break;
     }
   }
@@ -1608,7 +1463,7 @@ __device__ __forceinline__ void sparsity_count2_body(int bx, int b, int gx, cons
       if (c[i] < thr1) { v[2] += 1.f; v[3] += sp; }
     }
   }
-  const float r = block_sum_dpp<4, SP_NT>(v, red);
+  const float r = block_sum<4, SP_NT, wsum_dpp>(v, red);
   if (threadIdx.x < 4) part[((size_t)b * gx + bx) * 4 + threadIdx.x] = r;
 }
 
@@ -1691,7 +1546,7 @@ __device__ __forceinline__ void disp_finish4_body(int bx, int b, int gx, const D
   float w1 = 0.f, w2 = 0.f, w3 = 0.f;
   if (ground) { w1 = pre[b * PRE_STRIDE + 2]; w2 = pre[b * PRE_STRIDE + 3]; w3 = pre[b * PRE_STRIDE + 4] + tol; }      // Trainer.py:437-438
   float* g_disp = ground ? sc.g_disp : g_norm;
-  const float inv_me = 1.f / me, shiftc = dot / (me * me * static_cast<float>(n));
+  const float shiftc = dot / (me * me * static_cast<float>(n));
   constexpr int Q = FIN_PXT / 4;
   float4 G[Q], T[Q], D[Q];
 #pragma unroll
@@ -1734,9 +1589,8 @@ __device__ __forceinline__ void disp_finish4_body(int bx, int b, int gx, const D
     }
     if (g_disp) *reinterpret_cast<float4*>(g_disp + (size_t)b * n + p0) = make_float4(g0[0], g0[1], g0[2], g0[3]);
   }
-  (void)inv_me;
   if (ground) {
-    const float r = block_sum_dpp<1, GP_NT>(v, red);
+    const float r = block_sum<1, GP_NT, wsum_dpp>(v, red);
     if (threadIdx.x == 0) hinge_part[(size_t)b * gx + bx] = r;
   }
 }
@@ -1769,7 +1623,7 @@ __device__ __forceinline__ void image_fold_body(int b, const DDRegScale& sc, con
       for (int k = 0; k < NSMOOTH; ++k) v[k] += r[k];
     }
   }
-  const float r = block_sum_dpp<NSMOOTH, GP_NT>(v, red);       // value k valid in thread k
+  const float r = block_sum<NSMOOTH, GP_NT, wsum_dpp>(v, red);       // value k valid in thread k
   float me = 1.f;
   if (normalised) me = plane_mean(mean, b, n) + 1e-7f;           // (barrier inside: uniform condition)
   if ((int)threadIdx.x < NSMOOTH) {
@@ -1804,26 +1658,28 @@ __device__ __forceinline__ void image_fold_body(int b, const DDRegScale& sc, con
 }
 
 // =================================================================================================
-// all regularisers of all scales in up to five launches (dd_reg_losses)
+// all regularisers of all scales in up to four stage launches (dd_reg_losses_finish)
 // =================================================================================================
 // The per-term bodies above run as TASKS of one stage kernel launched per stage: a task owns a contiguous range of workgroups of
 // the launch and maps it onto a 2-D grid (x: blocks of a plane, y: image).  Stage 1: per-image disparity means, static-pixel
 // counts, RANSAC candidates.  Stage 2 (needs stage 1): smoothness of ALL entries of a scale in one pass (value + gradient),
-// sparsity gradient, candidate scoring.  Stage 3 (needs stage 2): smoothness sums per entry, inlier counts per candidate.
-// Stage 4: ONE pass over the disparity gradient -- mean-normalisation adjoint + ground hinge.  Stage 5: fixed-order fold of the
-// hinge partials; dd_reg_losses_finish folds them inside the assembling kernel instead (one launch less).  No global atomics.
-// Round 3: stage 2 evaluated the edge weights once per smoothed CHANNEL (5 tasks per scale in fine_tune, 45 000 workgroups of
-// ~30 loads each, 155 us) and the disparity gradient was rewritten twice (stages 3 and 4).
+// sparsity gradient; candidate scoring (ground_score_all_kernel).  Stage 3 (needs stage 2): smoothness sums per entry, per-image
+// scalars of the disparity finish.  Stage 4: ONE pass over the disparity gradient -- mean-normalisation adjoint + ground hinge.
+// The hinge partials are folded in a fixed order inside the assembling kernel (finish_kernel).  No global atomics.
+// The edge weights are evaluated once per pixel, not once per smoothed CHANNEL (5 tasks per scale in fine_tune, 45 000 workgroups of
+// ~30 loads each, 155 us), and the disparity gradient is rewritten once.
 constexpr int RT_NT = 256;
-static_assert(SM_NT == RT_NT && SP_NT == RT_NT && GP_NT == RT_NT, "one workgroup size for every task");
-enum : int { K_MEAN = 0, K_SPCOUNT, K_GCAND, K_SMOOTHALL, K_SPGRAD, K_GSCORE, K_SMFOLD, K_GCOUNT, K_DISPFIN, K_GFOLD, K_DISPPRE, K_IMGFOLD,
-              K_SPCOUNT2, K_SPGRAD2, K_DISPFIN4 };
+static_assert(SM_NT == RT_NT && SP_NT == RT_NT && GP_NT == RT_NT && RT_NT_FUSED == RT_NT, "one workgroup size for every task");
+// The values are the bit numbers of the DD_REG_SKIP mask (scripts/reg_task_costs.sh): 7 and 9 belonged to retired tasks, 5 switches
+// ground_score_all_kernel off.
+enum : int { K_MEAN = 0, K_SPCOUNT = 1, K_GCAND = 2, K_SMOOTHALL = 3, K_SPGRAD = 4, K_SMFOLD = 6, K_DISPFIN = 8, K_DISPPRE = 10,
+              K_IMGFOLD = 11, K_SPCOUNT2 = 12, K_SPGRAD2 = 13, K_DISPFIN4 = 14 };
 constexpr int REG_MAX_TASKS = 32;
 
 struct RegTask {
   int first;            // first workgroup of the task
   int gx;               // width of its virtual grid
-  int gx2;              // K_GCOUNT: records per image
+  int gx2;              // K_DISPPRE, K_IMGFOLD, K_SPGRAD2: records per image of the pass in front
   short kind;
   signed char scale, idx;
 };
@@ -1843,7 +1699,21 @@ struct RegOffsets {     // float offsets into DDRegArgs.workspace
   FoldSource fold[DD_MAX_SCALES];            // dd_fused_loss: where image_fold_body finds the scale's smoothness records
 };
 
-__global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, const RegOffsets off, const RegTasks tasks) {
+// workgroups that cover n pixels at pxt pixels per thread
+constexpr DD_HD int blocks_for(int n, int pxt) { return (n + RT_NT * pxt - 1) / (RT_NT * pxt); }
+
+// the mean-normalised smoothness entry of a scale (the planner admits one), or -1
+DD_HD int normalised_entry(const DDRegScale& sc) {
+  int e_norm = -1;
+#pragma unroll
+  for (int e = 0; e < DD_REG_SMOOTH; ++e)
+    if (sc.smooth[e].inp && sc.smooth[e].normalise) e_norm = e;
+  return e_norm;
+}
+
+// waves_per_eu(5): the kernel sits at the edge of a register granule (95 VGPRs with the two retired scoring tasks, 98 without them at
+// the compiler's own choice); five waves per SIMD are what it has always run with, and the allocator reaches them without scratch.
+__global__ __launch_bounds__(RT_NT) __attribute__((amdgpu_waves_per_eu(5))) void reg_stage_kernel(const DDRegArgs a, const RegOffsets off, const RegTasks tasks) {
   int ti = 0;
   for (int i = 1; i < tasks.n; ++i)
     if ((int)blockIdx.x >= tasks.t[i].first) ti = i;
@@ -1852,7 +1722,8 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
   const int s = t.scale, k = t.idx;
   const DDRegScale& sc = a.scale[s];
   const int B = a.B, h = sc.h, w = sc.w, n = h * w;
-  const int nblk_sm = (n + RT_NT * SMA_PXT - 1) / (RT_NT * SMA_PXT);          // smoothness records per image
+  const int nblk_sm = blocks_for(n, SMA_PXT);          // smoothness records per image
+  const int normalised = normalised_entry(sc);
   float* ws = a.workspace;
   float* res = a.res + s * DD_REG_RES_STRIDE;
   const float inv_total = 1.f / (static_cast<float>(B) * static_cast<float>(n));
@@ -1872,12 +1743,8 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
       break;
     case K_SMOOTHALL: {
       float* part[SMA_MAX_ENTRIES];
-      int normalised = -1;
 #pragma unroll
-      for (int e = 0; e < SMA_MAX_ENTRIES; ++e) {
-        part[e] = sc.smooth[e].inp ? ws + off.sm_part[s][e] : nullptr;
-        if (sc.smooth[e].inp && sc.smooth[e].normalise) normalised = e;
-      }
+      for (int e = 0; e < SMA_MAX_ENTRIES; ++e) part[e] = sc.smooth[e].inp ? ws + off.sm_part[s][e] : nullptr;
       const float* mean = normalised >= 0 ? ws + off.mean[s] : nullptr;
       float* g_tmp = normalised >= 0 ? ws + off.sm_gtmp[s][normalised] : nullptr;
       switch (k) {           // k = number of smoothed channels of the scale
@@ -1895,24 +1762,12 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
         sparsity_grad_body<SPG_PXT>(bx, by, gx, sc.delta[f], sc.delta_sum[f], sc.prob[f], B, n, inv_total, sc.w_sparsity[f], ws + off.sp_part[s][f],
                                     sc.g_prob[f], res + 10 + 2 * f);
       break;
-    case K_GSCORE:      // (no plan adds this task any more: the scoring runs on the matrix pipe, in the post kernel)
-      ground_score_body(bx, by, gx, sc.disp, sc.inv_K, ws + off.g_cand[s], B, h, w, rows, a.max_it, a.tol, dp,
-                        reinterpret_cast<int*>(ws + off.g_counts[s]), reinterpret_cast<int*>(ws + off.g_cpart[s]));
-      break;
-    case K_GCOUNT:
-      ground_count_body(by, t.gx2, reinterpret_cast<const int*>(ws + off.g_cpart[s]), B, a.max_it,
-                        reinterpret_cast<int*>(ws + off.g_counts[s]));
-      break;
     case K_SMFOLD:
       smooth_fold_body(ws + off.sm_part[s][k], B * nblk_sm, res + 2 * k);
       break;
     case K_DISPPRE:
     case K_DISPFIN4:
     case K_DISPFIN: {
-      int normalised = -1;
-#pragma unroll
-      for (int e = 0; e < SMA_MAX_ENTRIES; ++e)
-        if (sc.smooth[e].inp && sc.smooth[e].normalise) normalised = e;
       const bool nrm = normalised >= 0 && sc.smooth[normalised >= 0 ? normalised : 0].g_inp != nullptr, ground = sc.disp != nullptr;
       if (t.kind == K_DISPPRE)
         disp_pre_body(by, sc, nblk_sm, nrm, ground, nrm ? ws + off.mean[s] : nullptr, nrm ? ws + off.sm_part[s][normalised] : nullptr,
@@ -1933,24 +1788,9 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
       sparsity_grad2_body(bx, by, gx, sc, B, n, inv_total, ws + off.sp_part[s][0], t.gx2, res);
       break;
     case K_IMGFOLD: {
-      int normalised = -1;
-#pragma unroll
-      for (int e = 0; e < SMA_MAX_ENTRIES; ++e)
-        if (sc.smooth[e].inp && sc.smooth[e].normalise) normalised = e;
       const bool nrm = normalised >= 0, ground = sc.disp != nullptr;
       image_fold_body(by, sc, off.fold[s], nrm, ground, nrm ? ws + off.mean[s] : nullptr, ground ? ws + off.g_cand[s] : nullptr,
                       ground ? reinterpret_cast<const int*>(ws + off.g_cpart[s]) : nullptr, t.gx2, B, a.max_it, ws + off.d_pre[s]);
-      break;
-    }
-    case K_GFOLD: {
-      // fixed-order fold of the hinge partials (a launch of its own: a last-workgroup-done counter costs one contended
-      // device-scope atomic per workgroup -- 7 560 of them took longer than the hinge pass itself)
-      __shared__ float red[RT_NT / 64];
-      const float* partials = ws + off.g_part[s];
-      float v[1] = {0.f};
-      for (int i = threadIdx.x; i < ((n + RT_NT * FIN_PXT - 1) / (RT_NT * FIN_PXT)) * B; i += RT_NT) v[0] += partials[i];
-      const float r = block_sum<1, RT_NT>(v, red);
-      if (threadIdx.x == 0) res[14] = r;
       break;
     }
     default:
@@ -1958,7 +1798,7 @@ __global__ __launch_bounds__(RT_NT) void reg_stage_kernel(const DDRegArgs a, con
   }
 }
 
-constexpr int REG_STAGES = 5;
+constexpr int REG_STAGES = 4;
 struct RegPlan {
   RegOffsets off;
   RegTasks stage[REG_STAGES];
@@ -1972,19 +1812,29 @@ struct RegPlan {
   long long pre_all;       // float offset of the per-image records of all scales ([scale][image][PRE_STRIDE])
 };
 
+static bool aligned16(const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; }
+
+// appends a task of gx * gy workgroups to a launch's list (nb: workgroups of the launch so far); 1 = the list is full
+static int add_task(RegTasks& T, int& nb, int kind, int s, int idx, int gx, int gy, int gx2 = 0) {
+  if (T.n >= REG_MAX_TASKS) return 1;
+  RegTask& t = T.t[T.n++];
+  t.first = nb; t.gx = gx; t.gx2 = gx2; t.kind = (short)kind; t.scale = (signed char)s; t.idx = (signed char)idx;
+  nb += gx * gy;
+  return 0;
+}
+
 // does the smoothness of this launch qualify for smooth_quad_kernel?  Every scale that smooths anything must smooth the same number
 // of channels (1 | 3 | 4 | 5: what the four phases produce with shared tensors) in rows of whole, 16-byte aligned quads.
 static int quad_channels(const DDRegArgs& a) {
-  auto aligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; };
   int common = 0;
   for (int s = 0; s < a.num_scales; ++s) {
     const DDRegScale& sc = a.scale[s];
     int nch = 0;
-    bool ok = (sc.w % 4 == 0) && aligned(sc.img) && aligned(a.workspace);
+    bool ok = (sc.w % 4 == 0) && aligned16(sc.img) && aligned16(a.workspace);
     for (int k = 0; k < DD_REG_SMOOTH; ++k) {
       if (!sc.smooth[k].inp) continue;
       nch += sc.smooth[k].C;
-      ok = ok && aligned(sc.smooth[k].inp) && aligned(sc.smooth[k].g_inp);
+      ok = ok && aligned16(sc.smooth[k].inp) && aligned16(sc.smooth[k].g_inp);
     }
     if (nch == 0) continue;
     if (!ok || (common && nch != common)) return 0;
@@ -2006,34 +1856,26 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
   memset(&p.score, 0, sizeof(p.score));
   p.score.num_scales = a.num_scales; p.score.B = a.B; p.score.max_it = a.max_it; p.score.tol = a.tol;
   p.score.dp = depth_params(a.min_depth, a.max_depth);
-  auto add = [&](int st, int kind, int s, int idx, int gx, int gy, int gx2 = 0) -> int {
-    RegTasks& T = p.stage[st];
-    if (T.n >= REG_MAX_TASKS) return 1;
-    RegTask& t = T.t[T.n++];
-    t.first = p.blocks[st]; t.gx = gx; t.gx2 = gx2; t.kind = (short)kind; t.scale = (signed char)s; t.idx = (signed char)idx;
-    p.blocks[st] += gx * gy;
-    return 0;
-  };
+  auto add = [&](int st, int kind, int s, int idx, int gx, int gy, int gx2 = 0) { return add_task(p.stage[st], p.blocks[st], kind, s, idx, gx, gy, gx2); };
   int bad = 0;
   const long long pre_all = take((size_t)DD_MAX_SCALES * a.B * PRE_STRIDE);      // per-image records, scale-major, one block
   p.pre_all = pre_all;
   for (int s = 0; s < a.num_scales; ++s) {
     const DDRegScale& sc = a.scale[s];
     if (sc.h < 2 || sc.w < 2) return 1;
-    p.off.post_part[s] = take((size_t)a.B * ((sc.h * sc.w + RT_NT * 4 - 1) / (RT_NT * 4)) * 8);
-    p.off.d_pre[s] = pre_all + (long long)s * a.B * PRE_STRIDE;
     const int n = sc.h * sc.w;
-    const int nblk_sm = (n + RT_NT * SMA_PXT - 1) / (RT_NT * SMA_PXT), nblk_spg = (n + RT_NT * SPG_PXT - 1) / (RT_NT * SPG_PXT),
-              nblk_fin = (n + RT_NT * FIN_PXT - 1) / (RT_NT * FIN_PXT);
-    int normalised = -1, nch = 0;
+    p.off.post_part[s] = take((size_t)a.B * blocks_for(n, 4) * 8);
+    p.off.d_pre[s] = pre_all + (long long)s * a.B * PRE_STRIDE;
+    const int nblk_sm = blocks_for(n, SMA_PXT), nblk_spg = blocks_for(n, SPG_PXT), nblk_fin = blocks_for(n, FIN_PXT);
+    const int normalised = normalised_entry(sc);
+    int nch = 0;
     for (int k = 0; k < DD_REG_SMOOTH; ++k) {
       const DDRegSmooth& sm = sc.smooth[k];
       if (!sm.inp) continue;
       if (!sc.img || sm.C < 1 || (sm.normalise && sm.C != 1)) return 1;
       nch += sm.C;
       if (sm.normalise) {
-        if (normalised >= 0) return 1;                    // one mean buffer per scale
-        normalised = k;
+        if (k != normalised) return 1;                    // one mean buffer per scale
         p.off.mean[s] = take((size_t)a.B * MEAN_BPI);
         p.off.sm_gtmp[s][k] = take((size_t)a.B * n);
         bad |= add(0, K_MEAN, s, k, MEAN_BPI, a.B);
@@ -2076,8 +1918,7 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
     }
     if ((normalised >= 0 && sc.smooth[normalised].g_inp) || sc.disp) {
       const int rows_g = sc.disp ? (int)(a.g_prior * (float)sc.h) : 0;
-      const int score_rec = sc.disp ? (rows_g * sc.w + GS_SLABS * RT_NT - 1) / (GS_SLABS * RT_NT) : 0;
-      p.off.d_pre[s] = pre_all + (long long)s * a.B * PRE_STRIDE;
+      const int score_rec = sc.disp ? blocks_for(rows_g * sc.w, GS_SLABS) : 0;
       bad |= add(2, K_DISPPRE, s, 0, 1, a.B, score_rec);          // the image's scalars once (stage 3) ...
       bad |= add(3, K_DISPFIN, s, 0, nblk_fin, a.B);              // ... for the pixel pass (stage 4)
     }
@@ -2085,7 +1926,8 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
     for (int f = 0; f < DD_NUM_SRC; ++f) {
       if (!sc.prob[f]) continue;
       if (!sc.delta[f] || !sc.delta_sum[f]) return 1;
-      p.off.sp_part[s][f] = take((size_t)a.B * (SP_BPI * 2 > ((n + SP_NT * SP2_PXT - 1) / (SP_NT * SP2_PXT)) * 4 ? SP_BPI * 2 : ((n + SP_NT * SP2_PXT - 1) / (SP_NT * SP2_PXT)) * 4));
+      const int rec1 = SP_BPI * 2, rec2 = blocks_for(n, SP2_PXT) * 4;      // floats per image: K_SPCOUNT's records | K_SPCOUNT2's
+      p.off.sp_part[s][f] = take((size_t)a.B * (rec1 > rec2 ? rec1 : rec2));
       bad |= add(0, K_SPCOUNT, s, f, SP_BPI, a.B);
       if (!shared_prob) bad |= add(1, K_SPGRAD, s, f, nblk_spg, a.B);
     }
@@ -2097,9 +1939,9 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
       p.off.g_cand[s] = take((size_t)a.B * a.max_it * 3);
       p.off.g_counts[s] = take((size_t)a.B * a.max_it);
       p.off.g_part[s] = take((size_t)a.B * nblk_fin);
-      const int score_blocks = (rows * sc.w + GS_SLABS * RT_NT - 1) / (GS_SLABS * RT_NT);
+      const int score_blocks = blocks_for(rows * sc.w, GS_SLABS);
       p.off.g_cpart[s] = take((size_t)a.B * score_blocks * a.max_it);
-      bad |= add(0, K_GCAND, s, 0, (a.B * a.max_it + RT_NT - 1) / RT_NT, 1);
+      bad |= add(0, K_GCAND, s, 0, blocks_for(a.B * a.max_it, 1), 1);
       {
         ScoreScale& q = p.score.sc[s];
         q.disp = sc.disp; q.inv_K = sc.inv_K; q.cand = a.workspace + p.off.g_cand[s];
@@ -2107,11 +1949,21 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
         q.h = sc.h; q.w = sc.w; q.rows = rows; q.gx = score_blocks; q.first = p.score_blocks;
         p.score_blocks += score_blocks * a.B;
       }
-      bad |= add(4, K_GFOLD, s, 0, 1, 1);
     }
   }
   p.floats = total;
   return bad;
+}
+
+// where the assembling kernels find the per-workgroup hinge sums of the disparity finish
+static HingeFold hinge_fold(const DDRegArgs& a, const RegPlan& p) {
+  HingeFold hf;
+  for (int s = 0; s < DD_MAX_SCALES; ++s) {
+    const bool on = s < a.num_scales && a.scale[s].disp != nullptr;
+    hf.part[s] = on ? a.workspace + p.off.g_part[s] : nullptr;
+    hf.count[s] = on ? a.B * blocks_for(a.scale[s].h * a.scale[s].w, FIN_PXT) : 0;
+  }
+  return hf;
 }
 
 }  // namespace dd
@@ -2119,7 +1971,6 @@ static int reg_plan(const DDRegArgs& a, RegPlan& p) {
 using namespace dd;
 
 static inline int last_error() { return (int)hipGetLastError(); }
-#define T_FULL(T) ((T).n + 3 >= REG_MAX_TASKS)
 
 // ------------------------------------------------------------------------------------------------
 extern "C" size_t dd_smooth_workspace_bytes(int B, int C, int h, int w) {
@@ -2148,24 +1999,6 @@ extern "C" int dd_smooth_loss(const float* inp, const float* img, int B, int C, 
     else hipLaunchKernelGGL((smooth_kernel<false, false>), grid, dim3(SM_NT), 0, stream, inp, img, C, h, w, mean, wx, wy, g_inp, partials);
     hipLaunchKernelGGL((smooth_finish_kernel<false>), dim3(1, 1), dim3(SM_NT), 0, stream, partials, nblk, B * C, n, mean, g_tmp, g_inp, sums);
   }
-  return last_error();
-}
-
-// ------------------------------------------------------------------------------------------------
-extern "C" size_t dd_sparsity_workspace_bytes(int B, int h, int w) {
-  (void)h; (void)w;
-  return (size_t)B * SP_BPI * 2 * sizeof(float);
-}
-
-extern "C" int dd_sparsity_loss(const float* delta, const float* delta_sum, const float* prob, int B, int h, int w, float weight,
-                                float* g_prob, float* out, float* workspace, void* stream_) {
-  if (!delta || !delta_sum || !prob || !out || !workspace || B < 1) return (int)hipErrorInvalidValue;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int n = h * w;
-  const float inv_total = 1.f / ((float)B * n);
-  hipLaunchKernelGGL(sparsity_count_kernel, dim3(SP_BPI, B), dim3(SP_NT), 0, stream, delta, delta_sum, prob, n, inv_total, workspace);
-  hipLaunchKernelGGL(sparsity_grad_kernel, dim3((n + SP_NT - 1) / SP_NT, B), dim3(SP_NT), 0, stream, delta, delta_sum, prob, B, n,
-                     inv_total, weight, workspace, g_prob, out);
   return last_error();
 }
 
@@ -2263,7 +2096,8 @@ extern "C" size_t dd_reg_workspace_bytes(const DDRegArgs* a) {
   return (p.floats > 0 ? p.floats : 1) * sizeof(float);
 }
 
-static int reg_run(const DDRegArgs* a, void* stream_, const DDAssembleArgs* asmb, float* loss, float* out) {
+// the staged pipeline: up to four stage launches, then the hinge fold and the assembling in one kernel
+static int reg_run(const DDRegArgs* a, void* stream_, const DDAssembleArgs& asmb, float* loss, float* out) {
   if (!a || a->abi_version != DD_ABI_VERSION || a->B < 1 || a->num_scales < 1 || a->num_scales > DD_MAX_SCALES || !a->res || !a->workspace)
     return (int)hipErrorInvalidValue;
   RegPlan p;
@@ -2274,15 +2108,15 @@ static int reg_run(const DDRegArgs* a, void* stream_, const DDAssembleArgs* asmb
   {
     const char* e = getenv("DD_REG_SKIP");
     const int mask = e ? atoi(e) : 0;
+    constexpr int SKIP_BIT_SCORE = 5;                          // ground_score_all_kernel: a launch, not a task kind
     for (int st = 0; st < REG_STAGES; ++st)
       for (int i = 0; i < p.stage[st].n; ++i)
         if (mask & (1 << p.stage[st].t[i].kind)) p.stage[st].t[i].kind = 99;
     if (mask & (1 << K_SMOOTHALL)) p.quad_blocks = 0;          // (the smoothness kernel of its own)
-    if (mask & (1 << K_GSCORE)) p.score_blocks = 0;            // (the scoring kernel of its own)
+    if (mask & (1 << SKIP_BIT_SCORE)) p.score_blocks = 0;      // (the scoring kernel of its own)
   }
 #endif
-  // with an assembling request the last stage (the hinge fold) runs inside the assembling kernel
-  for (int st = 0; st < (asmb ? REG_STAGES - 1 : REG_STAGES); ++st) {
+  for (int st = 0; st < REG_STAGES; ++st) {
     if (st == 1 && p.quad_nch > 0 && p.quad_blocks > 0) {
       // the smoothness pass of every scale, behind the per-image means of stage 1
       switch (p.quad_nch) {
@@ -2305,17 +2139,8 @@ static int reg_run(const DDRegArgs* a, void* stream_, const DDAssembleArgs* asmb
     const int e = last_error();
     if (e) return e;
   }
-  if (asmb) {
-    HingeFold hf;
-    for (int s = 0; s < DD_MAX_SCALES; ++s) {
-      const bool on = s < a->num_scales && a->scale[s].disp != nullptr;
-      hf.part[s] = on ? a->workspace + p.off.g_part[s] : nullptr;
-      hf.count[s] = on ? a->B * ((a->scale[s].h * a->scale[s].w + RT_NT * FIN_PXT - 1) / (RT_NT * FIN_PXT)) : 0;
-    }
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, stream, a->res, hf, *asmb, loss, out);
-    return last_error();
-  }
-  return 0;
+  hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(256), 0, stream, a->res, hinge_fold(*a, p), asmb, loss, out);
+  return last_error();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2328,8 +2153,7 @@ static bool fused_eligible(const DDPhotoArgs& pa, const DDRegArgs& ra, int grp_e
   if (pa.min_depth != ra.min_depth || pa.max_depth != ra.max_depth || ra.max_it > GP_MAX_IT || ra.max_it < 1) return false;
   if (pa.mode != DD_MODE_RIGID && (!frames_share_tensors(pa) || pa.automask)) return false;       // (the auto-mask belongs to the rigid phase)
   if (!pa.workspace || !ra.workspace || !ra.res) return false;
-  auto aligned = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; };
-  if (!aligned(ra.workspace) || !aligned(pa.workspace)) return false;
+  if (!aligned16(ra.workspace) || !aligned16(pa.workspace)) return false;
   for (int s = 0; s < pa.num_scales; ++s) {
     const DDPhotoScale& ps = pa.scale[s];
     const DDRegScale& rs = ra.scale[s];
@@ -2350,11 +2174,11 @@ static bool fused_eligible(const DDPhotoArgs& pa, const DDRegArgs& ra, int grp_e
       if (any && rs.img != pa.target) return false;              // the tile kernel takes the colours from its staged target
     } else {
       // the combine pass works on 16-byte quads whether it smooths or not
-      if (ps.w % 4 != 0 || !aligned(ps.g_disp)) return false;
-      if (pa.mode != DD_MODE_RIGID && (!aligned(ps.g_flow[0]) || ((size_t)ps.h * ps.w) % 4 != 0)) return false;
-      if (pa.mode == DD_MODE_FLOW_MASK && !aligned(ps.g_mask[0])) return false;
-      if (any && (!aligned(rs.img) || !aligned(ps.disp) || (pa.mode != DD_MODE_RIGID && !aligned(ps.flow[0])) ||
-                  (pa.mode == DD_MODE_FLOW_MASK && !aligned(ps.mask[0]))))
+      if (ps.w % 4 != 0 || !aligned16(ps.g_disp)) return false;
+      if (pa.mode != DD_MODE_RIGID && (!aligned16(ps.g_flow[0]) || ((size_t)ps.h * ps.w) % 4 != 0)) return false;
+      if (pa.mode == DD_MODE_FLOW_MASK && !aligned16(ps.g_mask[0])) return false;
+      if (any && (!aligned16(rs.img) || !aligned16(ps.disp) || (pa.mode != DD_MODE_RIGID && !aligned16(ps.flow[0])) ||
+                  (pa.mode == DD_MODE_FLOW_MASK && !aligned16(ps.mask[0]))))
         return false;
     }
     if (rs.disp && (rs.disp != ps.disp || rs.g_disp != ps.g_disp)) return false;
@@ -2366,10 +2190,9 @@ static bool fused_eligible(const DDPhotoArgs& pa, const DDRegArgs& ra, int grp_e
 // both frames on one motion_prob tensor, whole 16-byte aligned quads: the sparsity passes of this scale run as K_SPCOUNT2 / K_SPGRAD2
 // (one pass for both frames, the gradient written with plain stores)
 static bool sparsity_quads(const DDRegScale& rs) {
-  auto al16 = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; };
   const int n = rs.h * rs.w;
   return rs.prob[0] && rs.prob[0] == rs.prob[1] && rs.g_prob[0] == rs.g_prob[1] && n % 4 == 0 && rs.w % 4 == 0 && rs.delta[0] && rs.delta[1] &&
-         al16(rs.delta[0]) && al16(rs.delta[1]) && al16(rs.prob[0]) && rs.g_prob[0] && al16(rs.g_prob[0]) && rs.delta_sum[0] && rs.delta_sum[1];
+         aligned16(rs.delta[0]) && aligned16(rs.delta[1]) && aligned16(rs.prob[0]) && rs.g_prob[0] && aligned16(rs.g_prob[0]) && rs.delta_sum[0] && rs.delta_sum[1];
 }
 
 // part: 0 = all five launches, 1 = the tile kernel alone, 2 = the four behind it
@@ -2427,7 +2250,7 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
   }
   if (part == 1) return 0;
 
-  // ---- 2: footprint sums + smoothness | tile-record fold | scoring | disparity sums ----
+  // ---- 2: footprint sums + smoothness | tile-record fold | scoring ----
   PostArgs post;
   memset(&post, 0, sizeof(post));
   post.num_scales = S;
@@ -2444,7 +2267,7 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
     if (ps.shift == 0) continue;                 // gx stays 0: the tile kernel stored scale 0 itself
     const int n = ps.h * ps.w;
     q.img = ra->scale[s].img; q.fp = fp_base + fp_off[s]; q.h = ps.h; q.w = ps.w; q.shift = ps.shift;
-    q.gx = (n + RT_NT_FUSED * 4 - 1) / (RT_NT_FUSED * 4);
+    q.gx = blocks_for(n, 4);
     q.npad = (q.gx * B + 7) / 8 * 8;
     q.part = ws + p.off.post_part[s];
     q.g_tmp = fuse.sc[s].g_tmp;
@@ -2460,31 +2283,17 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
   post.fold.S = S; post.fold.B = B; post.fold.tiles = tiles;
   blocks += S + B;
   post.first_score = blocks;
-  post.score.num_scales = S; post.score.B = B; post.score.max_it = ra->max_it; post.score.np = ra->np_per_it; post.score.tol = ra->tol;
-  post.score.dp = depth_params(ra->min_depth, ra->max_depth);
-  int sblocks = 0;
-  for (int s = 0; s < S; ++s) {
-    post.score.sc[s] = p.score.sc[s];
-    post.score.sc[s].first = sblocks;
-    if (ra->scale[s].disp) {
-      sblocks += p.score.sc[s].gx * B;            // (candidates: solved by the tile kernel's extra workgroups, read from p.score.sc[s].cand)
-    } else {
-      post.score.sc[s].gx = 0;
-    }
-  }
-  blocks += sblocks;
-  post.first_mean = blocks;
-  // (the per-image disparity sums: tile kernel's extra workgroups; the mean task of this kernel stays for callers without them)
+  post.score = p.score;           // (the candidates: solved by the tile kernel's side workgroups into p.score.sc[s].cand)
+  blocks += p.score_blocks;
 #ifdef DD_REG_DEBUG_SKIP
   // timing experiments only (variant build, scripts/post_task_costs.sh): DD_POST_SKIP = bit mask of post-kernel tasks whose workgroups
-  // return at once (1 combine + smoothness, 2 tile-record fold, 4 scoring, 8 disparity sums); the results are wrong then
+  // return at once (1 combine + smoothness, 2 tile-record fold, 4 scoring); the results are wrong then
   {
     const char* ev = getenv("DD_POST_SKIP");
     const int mask = ev ? atoi(ev) : 0;
     if (mask & 1) for (int s = 0; s < S; ++s) post.comb.sc[s].gx = 0;
     if (mask & 2) post.fold.S = post.fold.B = 0, post.fold.tiles = 0;
     if (mask & 4) for (int s = 0; s < S; ++s) post.score.sc[s].gx = 0;
-    if (mask & 8) for (int s = 0; s < S; ++s) post.mean.inp[s] = nullptr;
   }
 #endif
   switch (nch) {
@@ -2500,17 +2309,13 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
   RegTasks mid, fin;
   mid.n = fin.n = 0;
   int mid_blocks = 0, fin_blocks = 0;
-  auto add = [](RegTasks& T, int& nb, int kind, int s, int idx, int gx, int gy, int gx2) {
-    RegTask& t = T.t[T.n++];
-    t.first = nb; t.gx = gx; t.gx2 = gx2; t.kind = (short)kind; t.scale = (signed char)s; t.idx = (signed char)idx;
-    nb += gx * gy;
-  };
+  int full = 0;
   unsigned long long slots = 0ull;
   for (int s = 0; s < S; ++s) {
     const DDRegScale& rs = ra->scale[s];
     const DDPhotoScale& ps = pa->scale[s];
     const int n = rs.h * rs.w;
-    const int nblk_spg = (n + RT_NT * SPG_PXT - 1) / (RT_NT * SPG_PXT), nblk_fin = (n + RT_NT * FIN_PXT - 1) / (RT_NT * FIN_PXT);
+    const int nblk_spg = blocks_for(n, SPG_PXT), nblk_fin = blocks_for(n, FIN_PXT);
     const bool any = grp_entry[s][0] >= 0 || grp_entry[s][1] >= 0 || grp_entry[s][2] >= 0;
     for (int g = 0; g < 3; ++g) slots |= (unsigned long long)(grp_entry[s][g] >= 0 ? 2 * grp_entry[s][g] : 15) << (4 * (s * 3 + g));
     FoldSource& fs = p.off.fold[s];
@@ -2523,31 +2328,28 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
         fs.rec = ws + p.off.post_part[s]; fs.count = post.comb.sc[s].gx; fs.stride = 8; fs.img_stride = post.comb.sc[s].gx * 8; fs.base = 0;
       }
     }
-    auto al16 = [](const void* q) { return (reinterpret_cast<unsigned long long>(q) & 15ull) == 0; };
     const bool quads = n % 4 == 0 && rs.w % 4 == 0;
     if (any || rs.disp) {
-      if (T_FULL(mid) || T_FULL(fin)) return fused_fail(5, (int)hipErrorInvalidValue);
-      add(mid, mid_blocks, K_IMGFOLD, s, 0, 1, B, rs.disp ? p.score.sc[s].gx : 0);
-      const bool fin4 = quads && al16(ps.g_disp) && al16(ps.disp) && (grp_entry[s][0] < 0 || al16(fuse.sc[s].g_tmp));
-      if ((grp_entry[s][0] >= 0) || rs.disp) add(fin, fin_blocks, fin4 ? K_DISPFIN4 : K_DISPFIN, s, 0, nblk_fin, B, 0);
+      full |= add_task(mid, mid_blocks, K_IMGFOLD, s, 0, 1, B, rs.disp ? p.score.sc[s].gx : 0);
+      const bool fin4 = quads && aligned16(ps.g_disp) && aligned16(ps.disp) && (grp_entry[s][0] < 0 || aligned16(fuse.sc[s].g_tmp));
+      if ((grp_entry[s][0] >= 0) || rs.disp) full |= add_task(fin, fin_blocks, fin4 ? K_DISPFIN4 : K_DISPFIN, s, 0, nblk_fin, B);
     }
     if (sparsity_quads(rs)) {
       // both frames on one motion_prob tensor: one counting pass and one gradient pass for the two of them, plain stores
-      if (T_FULL(mid) || T_FULL(fin)) return fused_fail(6, (int)hipErrorInvalidValue);
-      const int gx2 = (n + SP_NT * SP2_PXT - 1) / (SP_NT * SP2_PXT);
-      add(mid, mid_blocks, K_SPCOUNT2, s, 0, gx2, B, 0);
-      add(fin, fin_blocks, K_SPGRAD2, s, 0, gx2, B, gx2);
+      const int gx2 = blocks_for(n, SP2_PXT);
+      full |= add_task(mid, mid_blocks, K_SPCOUNT2, s, 0, gx2, B);
+      full |= add_task(fin, fin_blocks, K_SPGRAD2, s, 0, gx2, B, gx2);
     } else {
       const bool one_tensor = rs.prob[0] && rs.prob[0] == rs.prob[1];
       for (int f = 0; f < DD_NUM_SRC; ++f) {
         if (!rs.prob[f]) continue;
-        if (T_FULL(mid) || T_FULL(fin)) return fused_fail(7, (int)hipErrorInvalidValue);
-        add(mid, mid_blocks, K_SPCOUNT, s, f, SP_BPI, B, 0);
-        if (!one_tensor) add(fin, fin_blocks, K_SPGRAD, s, f, nblk_spg, B, 0);
+        full |= add_task(mid, mid_blocks, K_SPCOUNT, s, f, SP_BPI, B);
+        if (!one_tensor) full |= add_task(fin, fin_blocks, K_SPGRAD, s, f, nblk_spg, B);
       }
-      if (one_tensor) add(fin, fin_blocks, K_SPGRAD, s, 2, nblk_spg, B, 0);
+      if (one_tensor) full |= add_task(fin, fin_blocks, K_SPGRAD, s, 2, nblk_spg, B);
     }
   }
+  if (full) return fused_fail(5, (int)hipErrorInvalidValue);
   if (mid_blocks > 0) {
     hipLaunchKernelGGL(reg_stage_kernel, dim3(mid_blocks), dim3(RT_NT), 0, stream, *ra, p.off, mid);
     e = last_error();
@@ -2559,15 +2361,9 @@ static int fused_run(const DDPhotoArgs* pa, const DDRegArgs* ra, const DDAssembl
     if (e) return fused_fail(104, e);
   }
   // ---- 5: the losses dict values ----
-  HingeFold hf;
-  for (int s = 0; s < DD_MAX_SCALES; ++s) {
-    const bool on = s < S && ra->scale[s].disp != nullptr;
-    hf.part[s] = on ? ws + p.off.g_part[s] : nullptr;
-    hf.count[s] = on ? B * ((ra->scale[s].h * ra->scale[s].w + RT_NT * FIN_PXT - 1) / (RT_NT * FIN_PXT)) : 0;
-  }
   ImageSums im;
   im.pre_all = ws + p.pre_all; im.slots = slots; im.B = B;
-  hipLaunchKernelGGL(fused_finish_kernel, dim3(1), dim3(256), 0, stream, ra->res, hf, im, *asmb, loss, out);
+  hipLaunchKernelGGL(fused_finish_kernel, dim3(1), dim3(256), 0, stream, ra->res, hinge_fold(*ra, p), im, *asmb, loss, out);
   return last_error();
 }
 
@@ -2591,11 +2387,9 @@ extern "C" int dd_fused_loss_supported(const DDPhotoArgs* photo, const DDRegArgs
   return 2;
 }
 
-extern "C" int dd_reg_losses(const DDRegArgs* a, void* stream_) { return reg_run(a, stream_, nullptr, nullptr, nullptr); }
-
 extern "C" int dd_reg_losses_finish(const DDRegArgs* a, const DDAssembleArgs* args, float* loss, float* out, void* stream_) {
   if (!args || !loss || !out || args->n < 0 || args->n > DD_MAX_RES || args->num_scales < 1 || args->num_scales > DD_MAX_SCALES || !a ||
       args->num_scales != a->num_scales)
     return (int)hipErrorInvalidValue;
-  return reg_run(a, stream_, args, loss, out);
+  return reg_run(a, stream_, *args, loss, out);
 }

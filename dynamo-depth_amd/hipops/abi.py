@@ -122,8 +122,6 @@ def declare(lib):
         "dd_photo_timing_read": (i, [C.POINTER(C.c_float), C.POINTER(i), i]),
         "dd_smooth_loss": (i, [v, v, i, i, i, i, i, f, v, v, v, v]),
         "dd_smooth_workspace_bytes": (z, [i, i, i, i]),
-        "dd_sparsity_loss": (i, [v, v, v, i, i, i, f, v, v, v, v]),
-        "dd_sparsity_workspace_bytes": (z, [i, i, i]),
         "dd_ground_loss": (i, [v, v, v, i, i, i, i, i, f, f, f, f, f, v, v, v, v, v]),
         "dd_ground_workspace_bytes": (z, [i, i, i, i]),
         "dd_resize_workspace_bytes": (z, [i, i, i, i, i]),
@@ -132,7 +130,6 @@ def declare(lib):
         "dd_ground_select": (i, [v, v, v, i, i, i, i, f, f, f, f, f, v, v, v, v, v, v]),
         "dd_ground_plane": (i, [v, v, i, i, i, i, i, f, f, v, v, v, v]),
         "dd_assemble_losses": (i, [v, C.POINTER(DDAssembleArgs), v, v, v]),
-        "dd_reg_losses": (i, [C.POINTER(DDRegArgs), v]),
         "dd_reg_losses_finish": (i, [C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v]),
         "dd_fused_loss": (i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v]),
         "dd_fused_loss_part": (i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v, i]),
@@ -249,8 +246,8 @@ def declare(lib):
 
 EXPORTED = (
     "dd_photo_loss", "dd_photo_workspace_bytes", "dd_photo_timing", "dd_photo_timing_read", "dd_photo_loss_part", "dd_smooth_loss", "dd_smooth_workspace_bytes",
-    "dd_sparsity_loss", "dd_sparsity_workspace_bytes", "dd_ground_loss", "dd_ground_workspace_bytes", "dd_ground_plane", "dd_ground_candidates", "dd_ground_select",
-    "dd_assemble_losses", "dd_reg_losses", "dd_reg_losses_finish", "dd_fused_loss", "dd_fused_loss_part", "dd_fused_loss_supported", "dd_reg_workspace_bytes", "dd_backproject", "dd_backproject_bwd", "dd_project3d", "dd_project3d_bwd", "dd_project3d_workspace_bytes",
+    "dd_ground_loss", "dd_ground_workspace_bytes", "dd_ground_plane", "dd_ground_candidates", "dd_ground_select",
+    "dd_assemble_losses", "dd_reg_losses_finish", "dd_fused_loss", "dd_fused_loss_part", "dd_fused_loss_supported", "dd_reg_workspace_bytes", "dd_backproject", "dd_backproject_bwd", "dd_project3d", "dd_project3d_bwd", "dd_project3d_workspace_bytes",
     "dd_ssim", "dd_ssim_bwd", "dd_disp_to_depth", "dd_pose_matrix", "dd_pose_matrix_bwd",
     "dd_channel_sum_nhwc", "dd_channel_sum_workspace_bytes", "dd_reflect_pad1_nhwc", "dd_reflect_pad1_nhwc_bwd",
     "dd_dwconv3x3_nhwc", "dd_dwconv3x3_nhwc_bwd_data", "dd_dwconv3x3_nhwc_bwd_weight", "dd_dwconv3x3_workspace_bytes", "dd_conv3x3_cout1_bwd_data",

@@ -122,15 +122,6 @@ int dd_smooth_loss(const float* inp, const float* img, int B, int C, int h, int 
                    float* g_inp, float* sums, float* workspace, void* stream);
 size_t dd_smooth_workspace_bytes(int B, int C, int h, int w);
 
-/* Motion-mask sparsity (Trainer.py:393-399): BCE-with-logits(prob, 0) over pixels whose disp_mag is below the
- * batch-global mean, only if every image keeps at least one such pixel.
- *   delta (B,h,w) from dd_photo_loss.out_delta, delta_sum = pointer to its global sum (device scalar),
- *   prob (B,1,h,w); out[0] = loss value (mean over static pixels, 0 if gated off), out[1] = #static pixels;
- *   g_prob (B,1,h,w) accumulate: weight * d loss/d prob.  workspace: dd_sparsity_workspace_bytes(B,h,w). */
-int dd_sparsity_loss(const float* delta, const float* delta_sum, const float* prob, int B, int h, int w, float weight,
-                     float* g_prob, float* out, float* workspace, void* stream);
-size_t dd_sparsity_workspace_bytes(int B, int h, int w);
-
 /* Above-ground term (Trainer.py:361-364,425-461; tools.GroundPlane tools.py:76-164).
  *   disp (B,1,h,w), inv_K (B,4,4) of this scale, rand_idx (B, max_it*np_per_it) int32 indices into the bottom
  *   int(g_prior*h) rows (the reference draws them with the host NumPy RNG, tools.py:125-127).
@@ -178,11 +169,11 @@ typedef struct DDAssembleArgs {
 } DDAssembleArgs;
 int dd_assemble_losses(const float* res, const DDAssembleArgs* args, float* loss, float* out, void* stream);
 
-/* All regularisers of Trainer.compute_losses for every scale in five launches (the per-term entry points above take two to
+/* All regularisers of Trainer.compute_losses for every scale in a handful of launches (the per-term entry points above take two to
  * four launches per term and scale -- about 45 per step at three scales); the smoothness of ALL smoothed tensors of a scale is
  * one pass that forms the edge weights once per pixel: edge-aware smoothness of disp / flow / mask
  * (tools.py:311-326, Trainer.py:355-359,380-381,401-402), mask sparsity (Trainer.py:393-399), ground term (Trainer.py:361-364,
- * 425-461).  Same per-element arithmetic as dd_smooth_loss / dd_sparsity_loss / dd_ground_loss; the smoothness sums are folded
+ * 425-461).  Same per-element arithmetic as dd_smooth_loss / dd_ground_loss; the smoothness sums are folded
  * per entry instead of per channel (a different, equally fixed order: the last bits of the value may differ from dd_smooth_loss).
  * A `smooth` entry with inp == NULL is skipped; the caller merges entries whose tensors are shared between the two frames
  * (weight = sum of the frames' weights).  A sparsity entry with prob == NULL and a ground entry with disp == NULL are skipped.
@@ -225,19 +216,20 @@ typedef struct DDRegArgs {
   float* workspace;                  /* dd_reg_workspace_bytes() bytes */
   DDRegScale scale[DD_MAX_SCALES];
 } DDRegArgs;
-int dd_reg_losses(const DDRegArgs* args, void* stream);
 size_t dd_reg_workspace_bytes(const DDRegArgs* args);
-/* dd_reg_losses followed by dd_assemble_losses on the same `res` record (args->res; the caller's photometric sums already sit
- * behind the regulariser slots) with one launch less: the fold of the ground-hinge partials runs inside the assembling kernel.
- * Four launches for the regularisers of all scales + one for the loss assembly (reference Trainer.py:355-409). */
+/* The regularisers above followed by dd_assemble_losses on the same `res` record (args->res; the caller's photometric sums already
+ * sit behind the regulariser slots): the fold of the ground-hinge partials runs inside the assembling kernel.  Four stage launches
+ * (plus one each for the quad smoothness and the candidate scoring) for the regularisers of all scales + one for the loss assembly
+ * (reference Trainer.py:355-409). */
 int dd_reg_losses_finish(const DDRegArgs* args, const DDAssembleArgs* assemble, float* loss, float* out, void* stream);
 
 /* THE fused loss: dd_photo_loss + dd_reg_losses_finish on the same arguments in FIVE launches instead of ten (round 5) -- the whole of
  * Trainer.generate_images_pred + Trainer.compute_losses and their backward (Trainer.py:215-411, tools.py:76-164,191-257,291-326):
  *   1  the photometric tile kernel; at scale 0 the edge-aware smoothness of the disparity / flow / mask (tools.py:311-326,
  *      Trainer.py:355-359,380-381,401-402) is evaluated in its store stage and added to the pixel's gradient before its one store;
+ *      extra workgroups of the same launch solve the RANSAC candidates (tools.py:114-154) and take the per-image disparity sums;
  *   2  one launch of tasks: low-res gradient footprints summed AND the smoothness of the scales >= 1 in the same pass | fold of the
- *      tile records | per-image disparity sums | RANSAC candidates + inlier counts (tools.py:114-154);
+ *      tile records | inlier counts of the candidates;
  *   3  static-pixel counts (Trainer.py:393-399) | per-image scalars: smoothness sums, mean, winning plane;
  *   4  sparsity gradient | mean-normalisation adjoint + ground hinge (Trainer.py:361-364,425-461);
  *   5  the losses dict values (Trainer.py:404-409).
