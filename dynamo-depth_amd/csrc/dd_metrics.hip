@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/dynamo_hip.h"
+#include "dd_bilinear.h"
 
 namespace dd {
 
@@ -63,17 +64,6 @@ __device__ float dm_select(const float* __restrict__ v, int M, int k, unsigned* 
   return __uint_as_float(prefix);
 }
 
-// F.interpolate(..., mode='bilinear', align_corners=False) source tap of destination index d (ATen: scale = in/out in float,
-// src = max(scale*(d+0.5)-0.5, 0))
-__device__ __forceinline__ void dm_tap(int d, float scale, int in_size, int& i0, int& i1, float& w1) {
-  float src = scale * (static_cast<float>(d) + 0.5f) - 0.5f;
-  if (src < 0.f) src = 0.f;
-  i0 = static_cast<int>(src);
-  if (i0 > in_size - 1) i0 = in_size - 1;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  w1 = src - static_cast<float>(i0);
-}
-
 // MASKED: `mask` (B, mask_h, mask_w) uint8 labels in ground-truth pixels; per_label (B,256,8) receives, for every label that
 // occurs among the sample's kept LiDAR points, the seven errors over those points and their count (tools.py:58-72).
 template <bool MASKED>
@@ -116,10 +106,7 @@ __global__ __launch_bounds__(DM_NT) void depth_metrics_kernel(const float* __res
       float wy, wx;
       dm_tap(row, sy, H, y0, y1, wy);
       dm_tap(col, sx, W, x0, x1, wx);
-      // ATen's upsample_bilinear2d: w0 = 1 - w1; value = wy0*(wx0*a + wx1*b) + wy1*(wx0*c + wx1*d)
-      const float top = (1.f - wx) * dp[y0 * W + x0] + wx * dp[y0 * W + x1];
-      const float bot = (1.f - wx) * dp[y1 * W + x0] + wx * dp[y1 * W + x1];
-      const float dv = (1.f - wy) * top + wy * bot;
+      const float dv = dm_blend(wy, wx, dp[y0 * W + x0], dp[y0 * W + x1], dp[y1 * W + x0], dp[y1 * W + x1]);
       g = z;
       p = 1.f / dv;
       cnt += 1.0;

@@ -1,2 +1,3 @@
 from .kitti_dataset import KITTIDataset  # noqa: F401
-from .synthetic import SyntheticTriplets, WaymoDataset, nuScenesDataset  # noqa: F401
+from .nuscenes_dataset import nuScenesDataset  # noqa: F401
+from .synthetic import SyntheticTriplets, WaymoDataset  # noqa: F401

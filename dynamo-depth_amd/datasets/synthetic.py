@@ -1,12 +1,13 @@
 """Synthetic triplets with the reference's item contract, for throughput runs without a dataset on disk
 (SURVEY.md 8(d)): low-frequency texture shifted by 2*f pixels between frames + pixel noise, KITTI-normalised
-intrinsics, ts = 1.  Waymo / nuScenes readers of the reference need the processed datasets (absent here); with
---synthetic their shapes are served by the same generator."""
+intrinsics, ts = 1.  The Waymo reader of the reference needs the processed dataset and cv2 (absent here); with --synthetic the
+datasets' shapes are served by the same generator.  load_mask=True adds labelled rectangles as motion / semantic masks."""
 import numpy as np
 import torch
 import torch.nn.functional as F
 import torch.utils.data as data
 
+NUM_SEM = 29                        # semantic labels of the synthetic masks: 0 .. 28 (the Waymo label count)
 NORMALISED_K = np.array([[0.58, 0, 0.5, 0], [0, 1.92, 0.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=np.float32)
 
 
@@ -20,13 +21,30 @@ def synth_frames(gen, height, width, frame_ids, shift=2):
     return out
 
 
+def synth_masks(gen, height, width, count=6):
+    """(sem_mask, mot_mask) (height,width) uint8: `count` rectangles over background 0, later ones on top; motion labels cycle
+    through 1 = moving, 2 = static, 3 = unlabelled so that every label occurs, semantic labels are drawn below NUM_SEM."""
+    sem = torch.zeros(height, width, dtype=torch.uint8)
+    mot = torch.zeros(height, width, dtype=torch.uint8)
+    for i in range(count):
+        y0 = int(torch.randint(0, height - height // 4, (1,), generator=gen))
+        x0 = int(torch.randint(0, width - width // 4, (1,), generator=gen))
+        dy = int(torch.randint(height // 16 + 1, height // 4 + 1, (1,), generator=gen))
+        dx = int(torch.randint(width // 16 + 1, width // 4 + 1, (1,), generator=gen))
+        mot[y0:y0 + dy, x0:x0 + dx] = 1 + i % 3
+        sem[y0:y0 + dy, x0:x0 + dx] = int(torch.randint(1, NUM_SEM, (1,), generator=gen))
+    return sem, mot
+
+
 class SyntheticTriplets(data.Dataset):
     def __init__(self, data_path=None, filenames=None, height=192, width=640, cam_name=None, img_type=None, frame_idxs=(0, -1, 1),
                  num_scales=3, is_train=False, img_ext=".jpg", load_depth=False, load_mask=False, path=False, length=None, seed=0):
         self.height, self.width, self.frame_idxs, self.num_scales = height, width, list(frame_idxs), num_scales
         self.length = length if length is not None else (len(filenames) if filenames is not None else 1024)
-        self.load_depth, self.seed = load_depth, seed
+        self.load_depth, self.load_mask, self.seed = load_depth, load_mask, seed
         self.max_lidar_num = 25000
+        self.full_res_shape = (2 * width, 2 * height)          # the masks' size: twice the frames', as ground truth outsizes the network input
+        self.categories = {l: "class_{:02d}".format(l) for l in range(NUM_SEM)}
 
     def __len__(self):
         return self.length
@@ -53,6 +71,8 @@ class SyntheticTriplets(data.Dataset):
             lidar = torch.stack([rows, cols, z], 1)
             item["depth_gt"] = torch.cat((lidar, torch.zeros(self.max_lidar_num - n, 3)))
             item["depth_valid"] = torch.cat((torch.ones(n), torch.zeros(self.max_lidar_num - n)))
+        if self.load_mask:
+            item["sem_mask"], item["mot_mask"] = synth_masks(gen, 2 * self.height, 2 * self.width)
         item["index"] = index
         return item
 
@@ -62,13 +82,10 @@ class _NeedsData(SyntheticTriplets):
 
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(
-            "the {} reader needs the processed dataset of the reference's prepare_data/ (not available in this build); "
-            "run with --synthetic to train on synthetic triplets of the {} shape".format(self.name, self.name))
+            "the {} reader needs the processed dataset of the reference's prepare_data/ and cv2 for the contour filling of its "
+            "masks (neither is available in this build); run with --synthetic to train on synthetic triplets of the {} "
+            "shape".format(self.name, self.name))
 
 
 class WaymoDataset(_NeedsData):
     name = "waymo"
-
-
-class nuScenesDataset(_NeedsData):
-    name = "nuscenes"

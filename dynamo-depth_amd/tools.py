@@ -6,6 +6,7 @@ GroundPlane, DepthMetrics, disp_to_depth, depth_to_disp, compute_smooth_loss, co
 Every differentiable operator is a torch.autograd.Function over the C ABI (hipops.functions); tensors must
 be on the GPU -- there is no CPU implementation of the loss path and none is silently substituted.
 (DepthMetrics is evaluation bookkeeping on gathered LiDAR hits and stays in plain torch.)
+MotionSegMetrics is the motion-mask evaluation of the reference's eval/motion_segmentation.py as an accumulating class.
 """
 import numpy as np
 import torch
@@ -120,6 +121,86 @@ def compute_errors(gt, pred):
     abs_rel = torch.mean(torch.abs(gt - pred) / gt)
     sq_rel = torch.mean((gt - pred) ** 2 / gt)
     return abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3
+
+
+class MotionSegMetrics:
+    """Precision / recall / F1 of the motion mask over `num_thrd` thresholds at ground-truth resolution, and the per-class tally of
+    false positives (reference eval/motion_segmentation.py:52-95,118-140), as ONE integer histogram: a pixel's bin is the number
+    of thresholds its up-sampled prediction exceeds, so tp / fp / fn of every threshold -- and the false positives of every class
+    at any threshold -- are suffix sums of `counts` (2 + num_sem, num_thrd + 1): row 0 = moving pixels (mot == 1), row 1 =
+    labelled pixels (mot != 3), row 2+l = labelled non-moving pixels of class l.  No (B, T, H, W) scan, no stored prediction, no
+    second pass.  The reference accumulates its sums in float32, inexact above 2**24 pixels; these are exact integers.
+
+    update() on CUDA tensors is one dd_motion_pr launch on the current stream (no host sync); CPU tensors take the same
+    formulation in torch.  `thrds` (optional) replaces the reference's table with any ascending 1-D table of num_thrd entries."""
+
+    def __init__(self, num_thrd=150, num_sem=0, thrds=None):
+        if not 1 <= num_thrd <= 256 or not 0 <= num_sem <= 32:
+            raise ValueError("MotionSegMetrics: 1 <= num_thrd <= 256 and 0 <= num_sem <= 32, got {} and {}".format(num_thrd, num_sem))
+        self.num_thrd, self.num_sem = int(num_thrd), int(num_sem)
+        if thrds is None:
+            eps = 1 / (num_thrd - 1)                             # as the reference builds it (eval/motion_segmentation.py:52-53)
+            thrds = torch.linspace(0 - eps, 1 - eps, num_thrd)
+        self.thrds = torch.as_tensor(thrds, dtype=torch.float32).reshape(-1).contiguous()
+        if self.thrds.numel() != self.num_thrd or bool((self.thrds[1:] < self.thrds[:-1]).any()):
+            raise ValueError("MotionSegMetrics: thrds must hold num_thrd ascending values")
+        self.counts = None
+
+    def reset(self):
+        self.counts = None
+
+    def update(self, pred_mask, mot_mask, sem_mask=None):
+        """pred_mask (B,1,h,w) float; mot_mask, sem_mask (B,H,W) uint8 on the same device."""
+        if pred_mask.dim() != 4 or pred_mask.shape[1] != 1 or mot_mask.dim() != 3 or mot_mask.shape[0] != pred_mask.shape[0]:
+            raise ValueError("MotionSegMetrics.update: pred_mask (B,1,h,w) and mot_mask (B,H,W), got {} and {}".format(
+                tuple(pred_mask.shape), tuple(mot_mask.shape)))
+        if self.num_sem > 0 and (sem_mask is None or sem_mask.shape != mot_mask.shape):
+            raise ValueError("MotionSegMetrics.update: num_sem > 0 needs a sem_mask of mot_mask's shape")
+        dev = pred_mask.device
+        pred = pred_mask.detach().to(torch.float32).contiguous()
+        mot = mot_mask.to(dev, torch.uint8).contiguous()
+        sem = sem_mask.to(dev, torch.uint8).contiguous() if self.num_sem > 0 else None
+        if self.counts is None:
+            self.counts = torch.zeros((2 + self.num_sem, self.num_thrd + 1), dtype=torch.int64, device=dev)    # the kernel's uint64, same bits
+        self.thrds = self.thrds.to(dev)
+        if pred.is_cuda:
+            from hipops import abi
+            B, _, h, w = pred.shape
+            L.check(L.load().dd_motion_pr(abi.ptr(pred), B, h, w, abi.ptr(mot), abi.ptr(sem), mot.shape[1], mot.shape[2], abi.ptr(self.thrds),
+                                          self.num_thrd, self.num_sem, abi.ptr(self.counts), L.current_stream()), "dd_motion_pr")
+        else:
+            self.counts += self._counts_torch(pred, mot, sem)
+
+    def _counts_torch(self, pred, mot, sem):
+        nb = self.num_thrd + 1
+        up = nn.functional.interpolate(pred, tuple(mot.shape[1:]), mode="bilinear", align_corners=False)[:, 0]
+        bins = torch.searchsorted(self.thrds, up.contiguous(), right=False)        # #{k : thrds[k] < value}
+        bins = torch.where(torch.isnan(up), torch.zeros_like(bins), bins)          # a NaN exceeds no threshold
+        rows = [torch.bincount(bins[mot == 1], minlength=nb), torch.bincount(bins[mot != 3], minlength=nb)]
+        rest = (mot != 1) & (mot != 3)
+        rows += [torch.bincount(bins[rest & (sem == l)], minlength=nb) for l in range(self.num_sem)]
+        return torch.stack(rows)
+
+    def compute(self):
+        if self.counts is None:
+            raise RuntimeError("MotionSegMetrics.compute() before any update()")
+        counts = self.counts.cpu()
+        above = counts.flip(1).cumsum(1).flip(1)[:, 1:]                             # [r, k] = sum over bins > k of row r
+        tp, p_sum = above[0], above[1]
+        fp, fn = p_sum - tp, counts[0].sum() - tp
+        tpd, fpd, fnd = tp.double(), fp.double(), fn.double()
+        precision = tpd / (tpd + fpd + 1e-10)
+        recall = tpd / (tpd + fnd + 1e-10)
+        f1 = 2 * (precision * recall) / (precision + recall + 1e-10)
+        best = int(torch.argmax(f1))
+        out = {"tp": tp, "fp": fp, "fn": fn, "precision": precision.float(), "recall": recall.float(), "f1": f1.float(),
+               "thrds": self.thrds.cpu(), "best_thrd_idx": best}
+        if self.num_sem > 0:
+            per_class = above[2:, best].tolist()
+            tally = {l: c for l, c in enumerate(per_class) if c > 0}                # the classes that occur, as np.unique lists them
+            tally["total"] = int(sum(per_class))
+            out["fp_tally"] = tally
+        return out
 
 
 class DepthMetrics(nn.Module):

@@ -382,6 +382,23 @@ int dd_depth_metrics_masked(const float* disp, int B, int H, int W, const float*
                             float* per_sample, float* mean, float* per_label, void* workspace, size_t workspace_bytes, void* stream);
 size_t dd_depth_metrics_masked_workspace_bytes(int B, int M);
 
+/* Motion-segmentation precision/recall counts in one pass (reference eval/motion_segmentation.py:52-95,118-140: the
+ * (B, T, H, W) `pred_mask > thrds` scan with its three sums per sample, and the second walk over the dataset for the
+ * false-positive tally).  pred [B,1,h,w] (outputs['motion_mask',-1,0]); mot, sem [B,H,W] uint8 labels in ground-truth pixels
+ * (mot: 1 = moving, 2 = static, 3 = unlabelled); thresholds [T] on the DEVICE.
+ * counts: (2 + num_sem, T + 1) uint64, ACCUMULATED into (caller zeroes once per evaluation).
+ * bin(p) = #{k : up(pred)(p) > thresholds[k]}   (strict; NaN -> bin 0), thresholds ascending, 1 <= T <= 256;
+ *          up() = F.interpolate(mode='bilinear', align_corners=False) from (h,w) to (H,W) in fp32 (a copy at equal sizes, as in ATen)
+ * row 0: pixels with mot == 1              by bin
+ * row 1: pixels with mot != 3              by bin
+ * row 2+l (l < num_sem <= 32): pixels with mot != 1 && mot != 3 && sem == l, by bin (sem may be NULL iff num_sem == 0;
+ *         labels >= num_sem are counted in no row)
+ * tp[k] / p_sum[k] of the reference = sum over bins > k of row 0 / row 1; false positives of class l at threshold k = the same
+ * sum of row 2+l.  Integer atomics only: the counts are exact and identical from run to run.  hipErrorInvalidValue for T or
+ * num_sem out of range, or sem == NULL with num_sem > 0. */
+int dd_motion_pr(const float* pred, int B, int h, int w, const uint8_t* mot, const uint8_t* sem, int H, int W,
+                 const float* thresholds, int T, int num_sem, unsigned long long* counts, void* stream);
+
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
  * bn2(+identity)->relu as used by networks/resnet_encoder.py:42-88, the stem bn1->relu, and LiteMono's BNGELU / DilatedConv.bn1
