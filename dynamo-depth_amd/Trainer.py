@@ -988,6 +988,11 @@ class Trainer:
         for key, value in inputs.items():
             if torch.is_tensor(value) and value.device != self.device:
                 inputs[key] = value.to(self.device, non_blocking=True)
+        if "mask_contours" in inputs:
+            # the motion masks arrive as contour records (datasets/base_dataset.py device_masks): one launch fills them
+            from hipops.contours import fill_contours
+            gh, gw = (int(x) for x in inputs["sem_mask"].shape[-2:])
+            inputs["mot_mask"] = fill_contours(inputs.pop("mask_vertices"), inputs.pop("mask_contours"), gh, gw)
         if groups is not None:
             from hipops.jpeg import decode_batch        # Huffman + IDCT + chroma up-sampling + colour conversion on the device
             data, hdr = inputs.pop("jpeg_bytes"), inputs.pop("jpeg_hdr")

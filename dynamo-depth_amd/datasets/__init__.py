@@ -1,3 +1,4 @@
 from .kitti_dataset import KITTIDataset  # noqa: F401
 from .nuscenes_dataset import nuScenesDataset  # noqa: F401
-from .synthetic import SyntheticTriplets, WaymoDataset  # noqa: F401
+from .synthetic import SyntheticTriplets  # noqa: F401
+from .waymo_dataset import WaymoDataset  # noqa: F401

@@ -2,6 +2,7 @@
 ('color',f,0), ('color_aug',f,0) (3,H,W) float in [0,1]; ('K',s), ('inv_K',s) (4,4) for every scale; ('ts',f);
 'gt_dim'; optionally 'depth_gt' (25000,3) [row, col, z] + 'depth_valid' (25000,); 'index'.
 torchvision is not available on the MI355X image, so ToTensor / Resize / ColorJitter are restated on PIL + torch."""
+import os
 import random
 
 import numpy as np
@@ -128,6 +129,12 @@ class BaseDataset(data.Dataset):
             self._device_decode = self._probe_device_decode()
         return self._device_decode
 
+    @property
+    def device_masks(self):
+        """Motion masks as contour records, filled on the device: with device_preprocess, for a dataset that stores contours
+        (get_mask_contours); DD_DEVICE_MASKS=0 keeps the host fill."""
+        return self.device_preprocess and hasattr(self, "get_mask_contours") and os.environ.get("DD_DEVICE_MASKS", "1") != "0"
+
     def _sample_parts(self, index):
         parts = self.filenames[index].split()
         return parts[0], int(parts[1]), (parts[2] if len(parts) == 3 else "l")
@@ -171,7 +178,7 @@ class BaseDataset(data.Dataset):
 
     def collate(self, samples):
         """DataLoader collate_fn: batches are uniform -- either every sample carries compressed frames (device decode) or every
-        sample carries pixels.  A batch with one host-decoded sample (see _compressed_frame) has its other samples decoded here
+        sample carries pixels, and either every sample carries its motion mask's contour records or every sample carries the mask.  A batch with one host-decoded sample (see _compressed_frame) has its other samples decoded here
         from the bytes they carry (PIL: the same pixels the device decoder produces, bit for bit)."""
         if any("frames_u8" in s for s in samples) and any("jpeg_bytes" in s for s in samples):
             import io
@@ -189,6 +196,13 @@ class BaseDataset(data.Dataset):
                             img = img.resize((self.width, self.height), Image.BICUBIC)      # the host-decoded sample came through _host_frame
                         frames.append(np.asarray(img, dtype=np.uint8))
                 s["frames_u8"] = torch.from_numpy(np.stack(frames))
+        if any("mask_contours" in s for s in samples) and any("mot_mask" in s for s in samples):
+            # one sample's contours exceeded the fixed records and it carries a host-filled mask: fill the others here, the same bytes
+            from hipops import contours
+            for s in samples:
+                if "mask_contours" in s:
+                    objects = contours.unpack(s.pop("mask_vertices").numpy(), s.pop("mask_contours").numpy())
+                    s["mot_mask"] = torch.from_numpy(contours.fill_host(objects, *s["sem_mask"].shape))
         return data.default_collate(samples)
 
     def __getitem__(self, index):
@@ -243,7 +257,16 @@ class BaseDataset(data.Dataset):
             pad = self.max_lidar_num - lidar.shape[0]
             item["depth_gt"] = torch.cat((lidar, torch.zeros(pad, 3)))
             item["depth_valid"] = torch.cat((torch.ones(lidar.shape[0]), torch.zeros(pad)))
-        if self.load_mask:
+        if self.load_mask and self.device_masks:
+            # the motion mask travels as its contours (17 KB for a Waymo frame against 2.46 MB) and is filled on the device
+            # (hipops.contours.fill_contours in Trainer.upload_inputs); a frame beyond the fixed records travels filled
+            sem, *mot = self.get_mask_contours(folder, frame, side)
+            item["sem_mask"] = torch.from_numpy(sem).type(torch.uint8)
+            if len(mot) == 2:
+                item["mask_vertices"], item["mask_contours"] = torch.from_numpy(mot[0]), torch.from_numpy(mot[1])
+            else:
+                item["mot_mask"] = torch.from_numpy(mot[0]).type(torch.uint8)
+        elif self.load_mask:
             sem, mot = self.get_mask(folder, frame, side, flip)
             item["sem_mask"] = torch.from_numpy(sem).type(torch.uint8)
             item["mot_mask"] = torch.from_numpy(mot).type(torch.uint8)

@@ -1,7 +1,6 @@
 """Synthetic triplets with the reference's item contract, for throughput runs without a dataset on disk
 (SURVEY.md 8(d)): low-frequency texture shifted by 2*f pixels between frames + pixel noise, KITTI-normalised
-intrinsics, ts = 1.  The Waymo reader of the reference needs the processed dataset and cv2 (absent here); with --synthetic the
-datasets' shapes are served by the same generator.  load_mask=True adds labelled rectangles as motion / semantic masks."""
+intrinsics, ts = 1.  With --synthetic every dataset's shape is served by this generator.  load_mask=True adds labelled rectangles as motion / semantic masks."""
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -76,16 +75,3 @@ class SyntheticTriplets(data.Dataset):
         item["index"] = index
         return item
 
-
-class _NeedsData(SyntheticTriplets):
-    name = "?"
-
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(
-            "the {} reader needs the processed dataset of the reference's prepare_data/ and cv2 for the contour filling of its "
-            "masks (neither is available in this build); run with --synthetic to train on synthetic triplets of the {} "
-            "shape".format(self.name, self.name))
-
-
-class WaymoDataset(_NeedsData):
-    name = "waymo"

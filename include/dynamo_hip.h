@@ -399,6 +399,17 @@ size_t dd_depth_metrics_masked_workspace_bytes(int B, int M);
 int dd_motion_pr(const float* pred, int B, int h, int w, const uint8_t* mot, const uint8_t* sem, int H, int W,
                  const float* thresholds, int T, int num_sem, unsigned long long* counts, void* stream);
 
+/* Motion masks from per-object contour lists (reference datasets/waymo_dataset.py:109-118: cv2.drawContours(..., -1, label, -1) per
+ * object): the exact integer fill of closed contours whose segments are horizontal, vertical or 45 degree diagonals (what
+ * cv2.findContours(CHAIN_APPROX_SIMPLE) emits) -- edge pixels and the even-odd interior over all contours of an object (half-open
+ * crossing rule: a segment counts on rows min(y0,y1) <= y < max(y0,y1)), the last object in file order wins; DESIGN 4.15.
+ * vertices (B,v_cap,2) int16 [x,y]; contours (B,c_cap,6) int32 records [first vertex, vertex count, object index, label 1..255,
+ * first row, last row], used records first and in file order (the contours of one object adjacent), a count of 0 ends the list;
+ * hipops/contours.py `pack` writes and validates them.  mask (B,H,W) uint8: every byte is written, by one launch, integers only.
+ * hipErrorInvalidValue for NULL pointers, non-positive sizes, H or W above 32768 (int16 vertices), B above 65535. */
+int dd_fill_contours(const int16_t* vertices, int v_cap, const int32_t* contours, int c_cap, int B, int H, int W, uint8_t* mask,
+                     void* stream);
+
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
  * bn2(+identity)->relu as used by networks/resnet_encoder.py:42-88, the stem bn1->relu, and LiteMono's BNGELU / DilatedConv.bn1
