@@ -22,14 +22,18 @@
 //   * 16 KB of halo + 9*NB KB of weights (34 KB at NB = 2), registers inside the launch bound: THREE workgroups per CU.  Every
 //     workgroup waits for its first halo, so occupancy is what pays: 32-channel chunks (64 KB, two workgroups per CU) lost to the
 //     library, four workgroups (128 VGPRs, spills) and a halo prefetch two chunks deep lost to this layout
-//     (profiles/r06_conv_half_variants.txt).
+//     (profiles/r06_conv_half_variants.txt);
+//   * store tail (dd_store_tile.h, shared with the fp32 kernels): the bias is fetched before the main loop, a tile inside the image
+//     with all of its channels stores its 32*NB registers straight-line (rounded once, 2-byte stores), edge tiles test every store.
 // The data gradient is the same kernel on the output gradient with the weights packed transposed and mirrored (pad' = 2 - pad).
 // The weight gradient is conv_half_wgrad_kernel below: fp32 result, one partial per workgroup, fixed-order fold (hipops/functions.py:
 // HalfConvFn runs all three; below 32 channels on either side its weight gradient stays with the library).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "../../include/dynamo_hip.h"
 #include "dd_attr.h"
+#include "dd_store_tile.h"
 
 namespace dd {
 namespace ch {
@@ -70,6 +74,11 @@ template <bool F16>
 __device__ __forceinline__ unsigned short pack1(float a) {
   return static_cast<unsigned short>(pack2<F16>(a, 0.f) & 0xffffu);
 }
+template <bool F16>
+struct StoreHalf {          // the rounding on the way out, for cm::store_acc32
+  typedef unsigned short type;
+  __device__ __forceinline__ unsigned short operator()(float v) const { return pack1<F16>(v); }
+};
 
 // pack layout: [n tile][chunk][tap][n block in tile][lane] x 16 bytes.  Lane l of a fragment holds, for output channel
 // (tile * NB + block) * 32 + (l & 31), the input channels chunk * 16 + (l >> 5) * 8 + 0..7 of the tap, converted from the fp32
@@ -215,6 +224,9 @@ __global__ __launch_bounds__(NT, MINWG) void conv_half_kernel(const unsigned sho
     }
   };
   const int last = nchunks - 1;
+  float bv[NB];          // what the epilogue adds, fetched first (dd_store_tile.h)
+#pragma unroll
+  for (int n = 0; n < NB; ++n) bv[n] = cm::tile_bias(bias, (ntile * NB + n) * 32 + (lane & 31), n_out, pack);
   fetch_a(0);
   fetch_b(0);
   for (int chunk = 0; chunk < nchunks; ++chunk) {
@@ -230,24 +242,21 @@ __global__ __launch_bounds__(NT, MINWG) void conv_half_kernel(const unsigned sho
     __builtin_amdgcn_sched_barrier(0);     // ... and the waits for them stay behind the block
   }
 
-  // C layout of 32x32: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+  // store tail (dd_store_tile.h): a tile inside Ho x Wo with all of its channels stores straight-line, edge tiles test every store
+  auto tail = [&](auto full) {
 #pragma unroll
-  for (int n = 0; n < NB; ++n) {
-    const int co = (ntile * NB + n) * 32 + (lane & 31);
-    if (co >= n_out) continue;
-    const float bv = bias ? bias[co] : 0.f;
+    for (int n = 0; n < NB; ++n) {
+      const int co = (ntile * NB + n) * 32 + (lane & 31);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int Y = Y0 + 2 * wave + m;
-      if (Y >= Ho) continue;
-      unsigned short* row = y + (((size_t)b * Ho + Y) * Wo) * n_out + co;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int X = X0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (X < Wo) row[(size_t)X * n_out] = pack1<F16>(acc[m][n][r] + bv);
+      for (int m = 0; m < 2; ++m) {
+        const int Y = Y0 + 2 * wave + m, X = X0 + 4 * (lane >> 5);
+        unsigned short* p = y + (((size_t)b * Ho + Y) * Wo + X) * n_out + co;
+        cm::store_acc32<decltype(full)::value>(acc[m][n], bv[n], p, (size_t)n_out, (co < n_out && Y < Ho) ? Wo - X : 0, StoreHalf<F16>{});
       }
     }
-  }
+  };
+  if (X0 + TW <= Wo && Y0 + TH <= Ho && (ntile + 1) * (32 * NB) <= n_out) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 static size_t pack_bytes(int n_out, int k_in) {

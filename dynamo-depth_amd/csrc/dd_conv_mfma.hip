@@ -18,19 +18,27 @@
 //   * the weights are split and laid out in fragment order once per step (conv_mfma_pack_kernel): per (chunk, tap) the workgroup
 //     fetches 3*NB KB two steps ahead (registers -> LDS, double-buffered);
 //   * software pipeline: the fragments of step s + 1 are read into a second register set while the MFMAs of step s run, the next
-//     chunk's halo is fetched into registers seven steps ahead; one LDS-only barrier per step.
+//     chunk's halo is fetched into registers seven steps ahead; one LDS-only barrier per step;
+//   * store tail (dd_store_tile.h): the bias is fetched BEFORE the main loop and a tile that lies inside the image with all of its
+//     channels stores its 32*NB accumulator registers straight-line, no wait between two stores; edge tiles test every store.
+//     (Until this was written down the epilogue loaded the bias conditionally and used it inside the bounds-checked store blocks:
+//     the compiler put an s_waitcnt vmcnt(0) in front of EVERY store -- 31 / 64 / 95 of them at NB = 1 / 2 / 3 -- so each store
+//     waited for the previous one's acknowledgement, with both resident workgroups of a CU in that phase together.)
 // Tried and measured no better (round 5): starting the second resident workgroup of every CU 4-35 us late so that the two are out of
-// phase (165-199 against 167 us).  Tried and measured slower: persistent workgroups that walk over several tiles, fetch the next tile's first halo under the
-// current tile's last chunk and issue a finished tile's stores behind the next tile's staging -- 193 against 175 us: on gfx9 stores
-// count in vmcnt like loads, in order, so the first counted wait of the next tile (its weights) also waits for the 64 stores to land.
+// phase (165-199 against 167 us).  Tried and measured slower, WITH the serialised store tail of that time: persistent workgroups that
+// walk over several tiles, fetch the next tile's first halo under the current tile's last chunk and issue a finished tile's stores
+// behind the next tile's staging -- 193 against 175 us: on gfx9 stores count in vmcnt like loads, in order, so the first counted wait
+// of the next tile (its weights) also waits for the 64 stores to land.
 // LDS: 48 960 B of halo + 2 x 4*ceil(3*NB/4) KB of weights (65 KB at NB = 2): two workgroups per CU, one staging while the other multiplies.
 // The data gradient is the same kernel on the output gradient with the weights packed transposed and flipped (pad' = 2 - pad).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/dynamo_hip.h"
 #include "dd_attr.h"
 #include "dd_split.h"
+#include "dd_store_tile.h"
 
 namespace dd {
 namespace cm {
@@ -237,6 +245,10 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const float* __restric
   };
 
   const int nsteps = nchunks * 9;
+  // what the epilogue adds, fetched first: the loop's first counted wait covers it and no load is pending when the stores start
+  float bv[NB];
+#pragma unroll
+  for (int n = 0; n < NB; ++n) bv[n] = tile_bias(bias, (ntile * NB + n) * 32 + (lane & 31), n_out, pack);
   fetch_b(0);
   fetch(0);
   store_b(0);
@@ -275,24 +287,22 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const float* __restric
     }
   }
 
-  // C layout of 32x32: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+  // Store tail (dd_store_tile.h): accumulator row = pixel column X0 + ..., column = output channel.  A tile inside Ho x Wo with all of its
+  // channels (every launch of the step's big layers) stores straight-line; edge tiles test every store.
+  auto tail = [&](auto full) {
 #pragma unroll
-  for (int n = 0; n < NB; ++n) {
-    const int co = (ntile * NB + n) * 32 + (lane & 31);
-    if (co >= n_out) continue;
-    const float bv = bias ? bias[co] : 0.f;
+    for (int n = 0; n < NB; ++n) {
+      const int co = (ntile * NB + n) * 32 + (lane & 31);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const int Y = Y0 + 2 * wave + m;
-      if (Y >= Ho) continue;
-      float* row = y + (((size_t)b * Ho + Y) * Wo) * n_out + co;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int X = X0 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (X < Wo) row[(size_t)X * n_out] = acc[m][n][r] + bv;
+      for (int m = 0; m < 2; ++m) {
+        const int Y = Y0 + 2 * wave + m, X = X0 + 4 * (lane >> 5);
+        float* p = y + (((size_t)b * Ho + Y) * Wo + X) * n_out + co;
+        store_acc32<decltype(full)::value>(acc[m][n], bv[n], p, (size_t)n_out, (co < n_out && Y < Ho) ? Wo - X : 0, StoreF32{});
       }
     }
-  }
+  };
+  if (X0 + TW <= Wo && Y0 + TH <= Ho && (ntile + 1) * (32 * NB) <= n_out) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 // ---- small images: flat pixel tiles + a split of the contraction --------------------------------------------------------------------
@@ -417,6 +427,9 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_flat_kernel(const float* __re
   };
 
   const int s_last = c_end * 9 - 1;
+  float bv[NB];          // the bias goes in here only without a split (conv_flat_fold_kernel adds it otherwise); fetched first, as above
+#pragma unroll
+  for (int n = 0; n < NB; ++n) bv[n] = tile_bias(splits == 1 ? bias : nullptr, (ntile * NB + n) * 32 + (lane & 31), n_out, pack);
   fetch_b(c_begin * 9);
   fetch(c_begin);
   store_b(c_begin * 9);
@@ -451,20 +464,19 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_flat_kernel(const float* __re
 
   // splits == 1: the result (+ bias); else this split's partial sums, [split][pixel][channel]
   float* dst = out + (splits > 1 ? (size_t)split * M * n_out : 0);
+  auto tail = [&](auto full) {
 #pragma unroll
-  for (int n = 0; n < NB; ++n) {
-    const int co = (ntile * NB + n) * 32 + (lane & 31);
-    if (co >= n_out) continue;
-    const float bv = (splits == 1 && bias) ? bias[co] : 0.f;
+    for (int n = 0; n < NB; ++n) {
+      const int co = (ntile * NB + n) * 32 + (lane & 31);
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int p = p0 + (2 * wave + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (p < M) dst[(size_t)p * n_out + co] = acc[m][n][r] + bv;
+      for (int m = 0; m < 2; ++m) {
+        const int p = p0 + (2 * wave + m) * 32 + 4 * (lane >> 5);
+        store_acc32<decltype(full)::value>(acc[m][n], bv[n], dst + (size_t)p * n_out + co, (size_t)n_out, co < n_out ? M - p : 0, StoreF32{});
       }
     }
-  }
+  };
+  if (p0 + FLAT_MT <= M && (ntile + 1) * (32 * NB) <= n_out) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 // y = bias + the partial sums of the splits, in split order (float4 per thread; M * n_out is a multiple of 4)

@@ -15,12 +15,16 @@
 //     (dd_mlp_pack, once per step) through LDS, each wave fetching its share.  (The first version read every lane's A fragment straight
 //     from global memory -- 32 cache lines per load instruction -- and every wave its own B fragments: correct, and bound by the
 //     texture addresser at 2-3x the time of this one.)
+//   * store tail of both kernels (dd_store_tile.h): the bias is fetched before the main loop, a tile with all of its rows and columns
+//     stores straight-line, edge tiles test every store.
 // Bound: HBM for the wide side (the 6C-wide tensor is written or read once, 4 bytes per element).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "../../include/dynamo_hip.h"
 #include "dd_attr.h"
 #include "dd_split.h"
+#include "dd_store_tile.h"
 
 namespace dd {
 namespace pw {
@@ -28,6 +32,9 @@ namespace pw {
 using cm::bf8;
 using cm::f16v;
 using cm::split2;
+using cm::store_acc32;
+using cm::StoreF32;
+using cm::tile_bias;
 
 constexpr int FRAG_U4 = 64;          // uint4 per fragment (64 lanes x 16 bytes)
 
@@ -193,6 +200,9 @@ __global__ __launch_bounds__(NW * 64, 2) void pw_gemm_kernel(const float* __rest
 
   const unsigned char* a_lane = smem + (wave * 32 * RB + (lane & 31)) * RSTR + (lane >> 5) * 16;
   const unsigned char* b_lane = s_b + lane * 16;
+  float bv[NG];          // what the epilogue adds, fetched first (dd_store_tile.h)
+#pragma unroll
+  for (int n = 0; n < NG; ++n) bv[n] = tile_bias(bias, (nb0 + n) * 32 + (lane & 31), N, pack);
   fetch(0);
   for (int c = 0; c < NCH; ++c) {
     lds_barrier();                         // the previous chunk's fragment reads are done
@@ -220,21 +230,20 @@ __global__ __launch_bounds__(NW * 64, 2) void pw_gemm_kernel(const float* __rest
                                                                  acc[rb][n], 0, 0, 0);
     }
   }
-  // C layout of 32x32: column = lane & 31, row = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)
+  // store tail (dd_store_tile.h): a tile with all of its rows and columns stores straight-line, edge tiles test every store
+  auto tail = [&](auto full) {
 #pragma unroll
-  for (int n = 0; n < NG; ++n) {
-    const int co = (nb0 + n) * 32 + (lane & 31);
-    if (nb0 + n >= NBLK || co >= N) continue;
-    const float bv = bias ? bias[co] : 0.f;
+    for (int n = 0; n < NG; ++n) {
+      const int co = (nb0 + n) * 32 + (lane & 31);
 #pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = row0 + (wave * RB + rb) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (row < M) y[(size_t)row * N + co] = acc[rb][n][r] + bv;
+      for (int rb = 0; rb < RB; ++rb) {
+        const int row = row0 + (wave * RB + rb) * 32 + 4 * (lane >> 5);
+        store_acc32<decltype(full)::value>(acc[rb][n], bv[n], y + (size_t)row * N + co, (size_t)N, co < N ? M - row : 0, StoreF32{});
       }
     }
-  }
+  };
+  if (row0 + MT <= M && (nb0 + NG) * 32 <= N) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 template <int NW, int RB, int NG, bool GELU_IN>
@@ -331,6 +340,9 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict
     for (int r = 0; r < 16; ++r) acc2[n][r] = 0.f;
   const unsigned char* w_lane = smem + lane * 16;
 
+  float bv[NB2];         // the second bias, fetched first (dd_store_tile.h)
+#pragma unroll
+  for (int n = 0; n < NB2; ++n) bv[n] = tile_bias(b2, n * 32 + (lane & 31), C, pack2);
   fetch(0);
   for (int hb = 0; hb < NHB; ++hb) {
     lds_barrier();                       // the previous block's fragment reads are done (first pass: b1 is in place after the next one)
@@ -380,16 +392,14 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict
       }
     }
   }
+  auto tail = [&](auto full) {
+    const int row = row0 + 4 * hh;
 #pragma unroll
-  for (int n = 0; n < NB2; ++n) {
-    const int co = n * 32 + (lane & 31);
-    const float bv = b2[co];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-      if (row < M) y[(size_t)row * C + co] = acc2[n][r] + bv;
-    }
-  }
+    for (int n = 0; n < NB2; ++n)
+      store_acc32<decltype(full)::value>(acc2[n], bv[n], y + (size_t)row * C + n * 32 + (lane & 31), (size_t)C, M - row, StoreF32{});
+  };
+  if ((int)blockIdx.x * 128 + 128 <= M) tail(std::true_type{});
+  else tail(std::false_type{});
 }
 
 template <int C>
