@@ -653,6 +653,38 @@ int dd_adam_chunk(void);
 int dd_adam_multi(const DDAdamRecord* records, int n_records, const int* block_map, int n_blocks, void* aux, double lr, double beta1, double beta2,
                   double eps, double weight_decay, const float* grad_scale, const float* found_inf, void* stream);
 
+/* Segment visualisation panels on the device (reference eval/visualize.py:24-124 get_vis / combine_vis over Trainer.py:574-605 vis_motion,
+ * utils.py:103-164 cart2polar / hsv_to_rgb / score_map_vis; csrc/dd_vis.hip).  A panel is a dense (N, R*H, C*W, 3) uint8 RGB buffer: N frames
+ * of R x C tiles of H x W pixels.  `tiles` (host memory): n_tiles <= DD_VIS_MAX_TILES triples { kind, row, col }.
+ * dd_vis_frame, once per frame: from that frame's dense fp32 tensors color / ref_color (3,H,W), disp / motion_mask (1,H,W), complete_flow
+ * (3,H,W), K / inv_K / cam_T_cam (4,4) it writes the image tiles ((uint8)(x * 255) on x clamped to [0,1]) and the colour-map tiles
+ * (matplotlib's Normalize(vmin, vmax) and 256-entry lookup on fp32 data; `lut`: device memory, [2][256] words r | g << 8 | b << 16, the
+ * disparity map's table, then the mask's; NaN is black) into frame `frame` of the panel; for every flow tile it stores the pixel's flow
+ * magnitude and hue as two fp32 planes of `side` ((max_frames, flow tiles, 2, H, W), the flow tiles in list order) and folds the frame's
+ * largest magnitude into maxima[0] (the segment's) and maxima[1 + frame], max_frames + 1 floats the caller zeroes before a segment's first
+ * frame: integer atomic maxima on the bit patterns of non-negative floats, so run-to-run identical; nothing returns to the host.  An input
+ * that no listed tile reads may be NULL.
+ * dd_vis_flow_tiles, once per segment: colours the flow tiles of frames 0 .. n_frames - 1 from `side`, value = clamp(magnitude /
+ * (flow_mag_factor * (max + 1e-8)), 0, 1) with the segment's maximum (consistent_flow != 0) or the frame's own, read from `maxima` on
+ * the device; rgb = 1 - hsv_to_rgb(hue, 1, value); a list without flow tiles launches nothing.
+ * hipErrorInvalidValue: a NULL pointer that a listed tile needs, a non-positive size, a tile outside R x C, more than DD_VIS_MAX_TILES tiles,
+ * frame outside 0 .. max_frames - 1. */
+#define DD_VIS_MAX_TILES 16
+#define DD_VIS_IMG 0
+#define DD_VIS_REF_IMG 1
+#define DD_VIS_DISP 2
+#define DD_VIS_MASK 3
+#define DD_VIS_EGO_FLOW 4
+#define DD_VIS_IND_FLOW 5
+#define DD_VIS_COMP_FLOW 6
+#define DD_VIS_SAMP_FLOW 7
+int dd_vis_frame(const float* color, const float* ref_color, const float* disp, const float* motion_mask, const float* complete_flow, const float* K,
+                 const float* inv_K, const float* cam_T_cam, float min_depth, float max_depth, int H, int W, const int* tiles, int n_tiles, int R, int C,
+                 const uint32_t* lut, float disp_vmin, float disp_vmax, float mask_vmin, float mask_vmax, int frame, int max_frames, uint8_t* panel,
+                 float* side, float* maxima, void* stream);
+int dd_vis_flow_tiles(const float* side, const float* maxima, const int* tiles, int n_tiles, int R, int C, int H, int W, int n_frames,
+                      float flow_mag_factor, int consistent_flow, uint8_t* panel, void* stream);
+
 const char* dd_error_string(int code);
 int dd_abi_version(void);
 
