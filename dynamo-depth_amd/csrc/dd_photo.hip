@@ -793,7 +793,9 @@ __global__ __launch_bounds__(NT, MIN_WAVES) void photo_tile_kernel(const DDPhoto
       f2 gu = sp2(0.f), gv = sp2(0.f);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
-        const f2 xv = S.pred[ch * R2N + oli];                 // re-read: frees registers across stage B
+        // re-read: frees registers across stage B.  A thread that overhangs the image never stored its position: whatever LDS held
+        // there (NaN included) must not reach its weight-0 products -- they are summed into the pose gradient
+        const f2 xv = own ? S.pred[ch * R2N + oli] : sp2(0.f);
         const float yv = S.tgt[ch * R2N + oli];
         const f2 gx = Sc[ch * 3 + 0] + xv * Sc[ch * 3 + 1] + sp2(yv) * Sc[ch * 3 + 2] + l1w * sign2(xv - sp2(yv));
         gu += gx * dvx[ch];

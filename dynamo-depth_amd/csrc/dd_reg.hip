@@ -102,6 +102,16 @@ __device__ __forceinline__ float plane_mean(const float* __restrict__ partial, i
 }
 
 // one thread per element of inp; writes the gradient w.r.t. the (normalised) input and per-block partials
+// A normalised value a / (mean + eps), rounded ONCE.  Written as a plain product, the compiler contracts `x * inv - y * inv` into
+// fma(x, inv, -round(y * inv)): two EQUAL inputs then differ by the product's rounding error instead of 0, and the term takes
+// sign(+-1e-8) where the reference has abs'(0) = 0 (tests/test_reg_terms_gpu.py, piecewise-constant disparity).
+// (the empty asm keeps the product a value of its own; __fmul_rn alone is contracted all the same)
+__device__ __forceinline__ float scaled(float a, float inv) {
+  float r = a * inv;
+  asm("" : "+v"(r));
+  return r;
+}
+
 template <bool HAS_IMG, bool NORMALISE>
 __device__ __forceinline__ void smooth_body(int bx, int by, int gx, const float* __restrict__ inp, const float* __restrict__ img, int C,
                                                         int h, int w, const float* __restrict__ mean, float wx_scale,
@@ -137,22 +147,22 @@ __device__ __forceinline__ void smooth_body(int bx, int by, int gx, const float*
       const float d = dd_abs(q0[0] - q1[0]) + dd_abs(q0[1] - q1[1]) + dd_abs(q0[2] - q1[2]);
       return __expf(-d / 3.f);
     };
-    const float ac = a_c * inv;
+    const float ac = scaled(a_c, inv);
     float g = 0.f;
     {                          // term owned by this pixel: |a[p] - a[p+1]| * wx[p]
-      const float d = ac - a_r * inv, e = edge_w(ic, ir);
+      const float d = ac - scaled(a_r, inv), e = edge_w(ic, ir);
       if (has_r) { acc[0] += dd_abs(d) * e; g += dd_sign(d) * e * wx_scale; }
     }
     {                          // term owned by the left neighbour
-      const float d = a_l * inv - ac, e = edge_w(il, ic);
+      const float d = scaled(a_l, inv) - ac, e = edge_w(il, ic);
       if (has_l) g -= dd_sign(d) * e * wx_scale;
     }
     {
-      const float d = ac - a_d * inv, e = edge_w(ic, id);
+      const float d = ac - scaled(a_d, inv), e = edge_w(ic, id);
       if (has_d) { acc[1] += dd_abs(d) * e; g += dd_sign(d) * e * wy_scale; }
     }
     {
-      const float d = a_u * inv - ac, e = edge_w(iu, ic);
+      const float d = scaled(a_u, inv) - ac, e = edge_w(iu, ic);
       if (has_u) g -= dd_sign(d) * e * wy_scale;
     }
     // NORMALISE: g_out is a temporary holding d/d(normalised input); otherwise it is the caller's accumulator
@@ -861,22 +871,22 @@ __device__ __forceinline__ void smooth_all_body(int bx, int b, int gx, const DDR
         if (c0 + j >= NCH) continue;           // compile-time
         const int ch = c0 + j;
         const float inv = nrm[ch] ? inv_mean : 1.f;
-        const float ac = a_c[j] * inv;
+        const float ac = scaled(a_c[j], inv);
         float g = 0.f, sx = 0.f, sy = 0.f;
         {
-          const float d = ac - a_r[j] * inv;
+          const float d = ac - scaled(a_r[j], inv);
           if (has_r) { sx = dd_abs(d) * e_r; g += dd_sign(d) * e_r * wxs[ch]; }
         }
         {
-          const float d = a_l[j] * inv - ac;
+          const float d = scaled(a_l[j], inv) - ac;
           if (has_l) g -= dd_sign(d) * e_l * wxs[ch];
         }
         {
-          const float d = ac - a_d[j] * inv;
+          const float d = ac - scaled(a_d[j], inv);
           if (has_d) { sy = dd_abs(d) * e_d; g += dd_sign(d) * e_d * wys[ch]; }
         }
         {
-          const float d = a_u[j] * inv - ac;
+          const float d = scaled(a_u[j], inv) - ac;
           if (has_u) g -= dd_sign(d) * e_u * wys[ch];
         }
         if (gp[ch]) gp[ch][p] = nrm[ch] ? g : g_old[j] + g;
@@ -989,7 +999,7 @@ __device__ __forceinline__ void smooth_quad_body(int bx, int b, const SmoothQuad
         const float old[4] = {G4[j].x, G4[j].y, G4[j].z, G4[j].w};
         float v[6];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) v[k] = raw[k] * inv;
+        for (int k = 0; k < 6; ++k) v[k] = scaled(raw[k], inv);
         float hd[5];                         // hd[k] = v[k] - v[k+1]: right term of pixel k-1, left term of pixel k
 #pragma unroll
         for (int k = 0; k < 5; ++k) hd[k] = v[k] - v[k + 1];
@@ -1001,11 +1011,11 @@ __device__ __forceinline__ void smooth_quad_body(int bx, int b, const SmoothQuad
           if (r_ok) { sx += dd_abs(hd[i + 1]) * eh[i + 1]; g += dd_sign(hd[i + 1]) * eh[i + 1] * wxs; }
           if (l_ok) g -= dd_sign(hd[i]) * eh[i] * wxs;
           {
-            const float d = v[i + 1] - dn[i] * inv;
+            const float d = v[i + 1] - scaled(dn[i], inv);
             if (has_d) { sy += dd_abs(d) * ed[i]; g += dd_sign(d) * ed[i] * wys; }
           }
           {
-            const float d = up[i] * inv - v[i + 1];
+            const float d = scaled(up[i], inv) - v[i + 1];
             if (has_u) g -= dd_sign(d) * eu[i] * wys;
           }
           gout[i] = nrm ? g : old[i] + g;

@@ -67,6 +67,7 @@ class Case:
             losses["loss"].backward()
         finally:
             orc.pixel_grid = grid32
+        self.outputs64, self.losses64 = outputs, losses
         g = {k: v.grad for k, v in leaves.items()}
         for f in (-1, 1):
             g[("T", f)] = outputs[("cam_T_cam", 0, f)].grad
