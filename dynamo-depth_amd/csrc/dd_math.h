@@ -332,16 +332,27 @@ struct SsimGrad {    // d ssim / d (mean_x, mean_xx, mean_xy), zero outside the 
 };
 
 DD_HD float ssim_value(const SsimStats& w, SsimGrad* grad) {
+  // Every product and sum below is rounded on its own, as in the reference's unfused arithmetic (no contraction: which products
+  // the compiler fuses differs between mx*mx + my*my + C1 and 2*mx*my + C1).  x and y then enter the pairs (a1, b1) and (a2, b2)
+  // through the same roundings: a window with x == y bit for bit gives n == d bit for bit and an SSIM of exactly 0, like
+  // ssim_value2 of dd_pair.h.  The caller's window sums have to treat sxx, syy and sxy alike for that (window_stats in dd_ops.hip).
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
   const float inv9 = 1.f / 9.f;
   const float mx = w.sx * inv9, my = w.sy * inv9;
-  const float vx = w.sxx * inv9 - mx * mx;
-  const float vy = w.syy * inv9 - my * my;
-  const float vxy = w.sxy * inv9 - mx * my;
-  const float a1 = 2.f * mx * my + kSsimC1, a2 = 2.f * vxy + kSsimC2;
-  const float b1 = mx * mx + my * my + kSsimC1, b2 = vx + vy + kSsimC2;
+  const float mxx = mx * mx, myy = my * my, mxy = mx * my;
+  const float vx = w.sxx * inv9 - mxx;
+  const float vy = w.syy * inv9 - myy;
+  const float vxy = w.sxy * inv9 - mxy;
+  const float a1 = 2.f * mxy + kSsimC1, a2 = 2.f * vxy + kSsimC2;
+  const float b1 = (mxx + myy) + kSsimC1, b2 = (vx + vy) + kSsimC2;
   const float n = a1 * a2, d = b1 * b2;
   const float inv_d = dd_rcp(d);
-  const float q = n * inv_d;                           // n/d
+  // n/d: the product with the reciprocal, then one step on the residual.  n * (1/d) alone can round d * (1/d) to 1 + 2^-23, a
+  // value of -6e-8 outside the clamp's pass band (val >= 0); with the step n == d gives exactly 1
+  const float q0 = n * inv_d;
+  const float q = fmaf(fmaf(-q0, d, n), inv_d, q0);
   const float val = (1.f - q) * 0.5f;
   if (grad) {
     const bool pass = (val >= 0.f) && (val <= 1.f);   // torch.clamp passes gradient on the closed interval

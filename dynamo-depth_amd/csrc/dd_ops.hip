@@ -171,6 +171,9 @@ __global__ __launch_bounds__(256) void fold16_kernel(const float* __restrict__ p
 
 // ---- SSIM ------------------------------------------------------------------------------------------
 __device__ __forceinline__ SsimStats window_stats(const float* __restrict__ x, const float* __restrict__ y, int X, int Y, int W, int H) {
+  // the three second moments take the taps through the same chain of fmas, written out: under contraction the compiler is free to
+  // form sxx as fma(x0, x0, round(x1*x1)) and sxy as fma(x1, y1, round(x0*y0)), and x == y then does not give sxx == sxy (ssim_value)
+#pragma clang fp contract(off)
   SsimStats st = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int j = -1; j <= 1; ++j) {
@@ -179,7 +182,7 @@ __device__ __forceinline__ SsimStats window_stats(const float* __restrict__ x, c
     for (int i = -1; i <= 1; ++i) {
       const int q = ry + dd_reflect(X + i, W);
       const float xv = x[q], yv = y[q];
-      st.sx += xv; st.sy += yv; st.sxx += xv * xv; st.syy += yv * yv; st.sxy += xv * yv;
+      st.sx += xv; st.sy += yv; st.sxx = fmaf(xv, xv, st.sxx); st.syy = fmaf(yv, yv, st.syy); st.sxy = fmaf(xv, yv, st.sxy);
     }
   }
   return st;

@@ -294,7 +294,8 @@ int dd_backproject_bwd(const float* g_points, const float* inv_K, int B, int h, 
  * pix (B,h,w,2) normalised to [-1,1], ego (B,3,N) */
 int dd_project3d(const float* points, const float* K, const float* T, int B, int h, int w, float eps,
                  float* pix, float* ego, void* stream);
-/* g_points (B,4,N) overwritten; g_T (B,4,4) overwritten (NULL when T is NULL); workspace B*nblocks*12 floats */
+/* g_points (B,4,N) overwritten; g_T (B,4,4) overwritten (NULL when T is NULL); workspace B*nblocks*16 floats
+ * (dd_project3d_workspace_bytes; nblocks = ceil(h*w / 256)).  g_pix or g_ego may be NULL: that output's upstream gradient is 0. */
 int dd_project3d_bwd(const float* points, const float* K, const float* T, const float* g_pix, const float* g_ego,
                      int B, int h, int w, float eps, float* g_points, float* g_T, float* workspace, void* stream);
 size_t dd_project3d_workspace_bytes(int B, int h, int w);
