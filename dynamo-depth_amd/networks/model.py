@@ -63,13 +63,9 @@ class Model(nn.Module):
     def forward(self, inputs):
         outputs = {}
         if getattr(self.opt, "multi_stream", False) and inputs["color_aug", 0, 0].is_cuda:
-            # Eager execution runs the branches side by side.  Under hipGraph capture the plain single-stream forward is
-            # recorded unless DD_MS_CAPTURE names a placement: parallel graph branches are faster (KITTI shape, B=12: 216-222
-            # img/s against 192 for the single-stream graph) but not dependable on this ROCm stack -- with motion encoder and
-            # decoders both on one side stream the replayed step turns non-finite within two updates, a fifth stream for
-            # the decoders crashes the capture inside the HIP runtime, and the placement that replays correctly at 192x640
-            # ("e": encoder on the capturing stream) hangs in replay at the Waymo shape 320x480 (scripts/debug_graph_ms.py).
-            if not torch.cuda.is_current_stream_capturing() or os.environ.get("DD_MS_CAPTURE"):
+            # Eager execution runs the branches side by side; under hipGraph capture the plain single-stream forward is recorded:
+            # parallel branches inside one captured graph are not dependable on this ROCm stack (HISTORY.md section 5, "Whole-step hipGraph").
+            if not torch.cuda.is_current_stream_capturing():
                 return self.forward_streams(inputs, outputs)
         self.predict_depths(inputs, outputs)
         self.predict_poses(inputs, outputs)
@@ -97,15 +93,6 @@ class Model(nn.Module):
         cur = tc.current_stream()
         self._main_stream = cur
         s_prev, s_next, s_pose, s_mot = self.side_streams()
-        dbg = os.environ.get("DD_MS_DEBUG", "")            # debugging: letters d / p / m keep that branch on the current stream
-        if tc.is_current_stream_capturing():
-            dbg += os.environ.get("DD_MS_CAPTURE", "")      # opt-in placements under capture (see forward)
-        if "d" in dbg:
-            s_prev = s_next = cur
-        if "p" in dbg:
-            s_pose = cur
-        if "m" in dbg:
-            s_mot = cur
         frames = list(self.opt.frame_ids)
         side = {}
         if not (getattr(self.opt, "skip_unused_depth_frames", False) and self.training):
@@ -141,19 +128,15 @@ class Model(nn.Module):
         with tc.stream(s_pose):
             self.predict_poses(inputs, outputs)
         motions = self.bool_CmpFlow or self.bool_MotMask
-        s_enc = cur if "e" in dbg else s_mot             # motion encoder and motion decoders are placed separately, see below
-        s_dec = cur if "c" in dbg else s_mot
         if motions:
-            with tc.stream(s_enc):
+            with tc.stream(s_mot):
                 self.predict_motion_feat(inputs, outputs)
         if predrawn.get(frames[0]) is not None:
             self.depth_enc.install_drop_masks(predrawn[frames[0]])
         self.predict_depths(inputs, outputs, frames=frames[:1])
         if motions:
-            s_dec.wait_stream(s_pose)                    # the decoders read the (detached) pose vectors
-            if s_dec is not s_enc:
-                s_dec.wait_stream(s_enc)
-            with tc.stream(s_dec):
+            s_mot.wait_stream(s_pose)                    # the decoders read the (detached) pose vectors
+            with tc.stream(s_mot):
                 self.predict_motions(inputs, outputs, feats_done=True)
         for st in self._streams:
             cur.wait_stream(st)

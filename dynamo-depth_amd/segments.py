@@ -25,8 +25,7 @@ non-finite within a few hundred steps; every graph is captured behind a cleared 
 on one stream and replayed on several would share one workspace); the host stays at most DD_SEG_RUN_AHEAD (2) steps ahead of the
 GPU; the step's cross-stream events live until the GPU has passed them.  Debugging switches: DD_SEG_CHECK=1 (finiteness of every
 buffer after each replay, with a host sync), DD_SEG_PROBE=1 (the same as device-side flags, no sync; probe_report()),
-DD_SEG_SERIAL=all|name,.. (those segments on the caller's stream), DD_SEG_CHECK_AT=k, DD_SEG_TIMING=1 (timeline()),
-DD_SEG_SIDE_LATE=0, DD_SEG_EXEC_GUARD=1.
+DD_SEG_TIMING=1 (timeline()).
 
 Multi-GPU: the parameter gradients of all segments live in ONE flat buffer (a contiguous slice per segment), averaged over the ranks
 (RCCL) by one all-reduce behind the last backward graph, in front of Adam's graph (DD_SEG_REDUCE=overlap: round 3's scheme, one
@@ -102,31 +101,17 @@ class SegmentedStep:
         self.total_replays = 0      # monotonic: what the DD_SEG_REDUCE=auto probe counts -- a checkpoint inside the probe (save_model ->
         self._bn_delta = []         # flush_counters) must neither restart it nor let one rank decide at another step than the others
         self.main = torch.cuda.Stream()             # capture stream of the segments that replay on the caller's stream (the
-        if os.environ.get("DD_STREAM_REPICK", "0") == "1":         # (experiment: measure the streams' queues again at capture time)
-            from hipops import queues
-            queues._cache.clear()
-            model._streams = None
         self.side_streams = list(model.side_streams())      # legacy default stream cannot capture)
-        self.side_late = os.environ.get("DD_SEG_SIDE_LATE", "1") != "0"
-        # WHEN the statistics-only side batch runs (it feeds nothing but the BatchNorm buffers, so any time between the inputs and the
-        # optimizer is correct): "start" = beside the forward passes, "loss" = beside the backward passes (issued behind the loss),
-        # "pose" = behind the pose backward on the pose stream (the backward's short branch)
-        self.side_at = os.environ.get("DD_SEG_SIDE_AT", "start") if self.side_late else "start"
         self.run_ahead = int(os.environ.get("DD_SEG_RUN_AHEAD", "2"))       # steps the host may be ahead of the GPU (0 = unbounded)
         self._ends = []
         self._events = []
         self.host_wait_s = 0.0
-        self.exec_guard = os.environ.get("DD_SEG_EXEC_GUARD", "0") == "1"      # (debugging: one launch of a graph exec in flight at a time)
-        self._last_launch = {}
-        self.serial = set(x for x in os.environ.get("DD_SEG_SERIAL", "").split(",") if x)
-        self.check_at = int(os.environ.get("DD_SEG_CHECK_AT", "-1"))
         self.probe = os.environ.get("DD_SEG_PROBE", "0") == "1"
         self._ring = None
         self.check = os.environ.get("DD_SEG_CHECK", "0") == "1"            # finiteness of every buffer after each replay (debugging)
         self.timing = os.environ.get("DD_SEG_TIMING", "0") == "1"       # events around every replay (timeline(); bench.py prints it)
         self.marks = []
         self.loss_events = None
-        self.hp_stream = torch.cuda.Stream(priority=-1) if os.environ.get("DD_SEG_PRIORITY", "0") == "1" else None
         self.time_tile_kernel = bool(getattr(trainer, "time_tile_kernel", False))
         self.static = {k: v.clone() for k, v in inputs.items() if torch.is_tensor(v) and not self._is_pyramid_key(k)}
         self.ddp = bool(self.opt.ddp and dist.is_available() and dist.is_initialized())
@@ -141,6 +126,8 @@ class SegmentedStep:
         # the faster one stays; `reduce_mode_chosen` / `reduce_probe_ms` tell bench.py which and by how much.  With one rank there is
         # nothing to hide: "end".
         self.reduce_mode = os.environ.get("DD_SEG_REDUCE", "auto" if self.world > 1 else "end")
+        if self.reduce_mode not in ("end", "overlap", "auto"):
+            raise ValueError("DD_SEG_REDUCE is end, overlap or auto, not {!r}".format(self.reduce_mode))
         self.reduce_probe_ms = None
         self._probe_marks = {"end": [], "overlap": []}
         if self.reduce_mode == "auto" and not self.ddp:
@@ -215,12 +202,10 @@ class SegmentedStep:
     def _capture(self):
         tr, model, o = self.tr, self.model, self.opt
         main = self.main
-        s_side, s_dec, s_pose, s_mot = self.side_streams
-        if os.environ.get("DD_SEG_DEC_STREAM", "shared") != "own":
-            # The decoders follow their encoder anyway: one stream for both leaves caller | side batch | pose | motion = four
-            # streams for the four hardware queues (networks.Model.side_streams picks them on distinct queues).  Round 3 gave
-            # the decoders a fifth stream, and pose shared a queue with the motion encoder: it ran behind it in both directions.
-            s_dec = s_mot
+        # The decoders follow their encoder anyway: one stream for both leaves caller | side batch | pose | motion = four
+        # streams for the four hardware queues (networks.Model.side_streams picks them on distinct queues).  Round 3 gave
+        # the decoders a fifth stream, and pose shared a queue with the motion encoder: it ran behind it in both directions.
+        s_side, _, s_pose, s_mot = self.side_streams
         frames = list(o.frame_ids)
         target, sources = frames[0], frames[1:]
         motions = bool(model.bool_CmpFlow or model.bool_MotMask)
@@ -255,23 +240,16 @@ class SegmentedStep:
                         yield
         torch.cuda.synchronize()
 
-        dbg = os.environ.get("DD_SEG_DEBUG", "")
-
-        def capture(seg, fn, stream, what="fwd"):
+        def capture(seg, fn):
             """Every graph is captured on ONE stream (self.main), whatever stream it is replayed on later: autograd ties
             each node to the stream of its forward and synchronises streams with events when gradients cross from one to
             another -- under capture such an event drags a second stream into the capture (the backward capture of a segment
             whose forward had been captured on another stream than the loss graph crashed inside hipStreamEndCapture)."""
-            if dbg:
-                print("[segments] capturing {} {}".format(seg.name, what), flush=True)
             g = torch.cuda.CUDAGraph()
-            stream = self.main if "m" not in dbg else stream
             self._private_blas_workspace()
             with _empty_graph_watch() as watch:
-                with torch.cuda.graph(g, pool=seg.pool, stream=stream, capture_error_mode=self.capture_mode):
+                with torch.cuda.graph(g, pool=seg.pool, stream=self.main, capture_error_mode=self.capture_mode):
                     res = fn()
-            if dbg:
-                print("[segments] captured  {} {}{}".format(seg.name, what, " (empty: not replayed)" if watch.empty else ""), flush=True)
             # a segment the phase gives nothing to do (the statistics-only batch of an eval-mode run, ...) is not replayed at all:
             # no launch, and no "graph is empty" warning that would be indistinguishable from an empty OPTIMIZER graph (an error below)
             return (None if watch.empty else g), res
@@ -282,7 +260,7 @@ class SegmentedStep:
 
         def f_inputs():
             tr.derive_inputs(batch)
-        seg.fwd, _ = capture(seg, f_inputs, main)
+        seg.fwd, _ = capture(seg, f_inputs)
         self.batch = batch
 
         # ---- forward graphs -----------------------------------------------------------------------------------------------
@@ -295,7 +273,7 @@ class SegmentedStep:
         def f_depth():
             with swap():
                 model.predict_depths(batch, outputs, frames=[target])
-        depth.fwd, _ = capture(depth, f_depth, main)
+        depth.fwd, _ = capture(depth, f_depth)
         self.segs.append(depth)
 
         self.collectors = []
@@ -309,7 +287,7 @@ class SegmentedStep:
                 self.collectors = cols
                 with swap():
                     model.predict_depths(batch, outputs, frames=list(sources), collectors=cols)
-            side.fwd, _ = capture(side, f_side, s_side)
+            side.fwd, _ = capture(side, f_side)
             self.segs.append(side)
 
         pose = _Segment("pose", s_pose)
@@ -317,7 +295,7 @@ class SegmentedStep:
         def f_pose():
             with swap():
                 model.predict_poses(batch, outputs)
-        pose.fwd, _ = capture(pose, f_pose, s_pose)
+        pose.fwd, _ = capture(pose, f_pose)
         self.segs.append(pose)
 
         # The motion encoder does not need the pose networks -- only the decoders read the (detached) pose vectors -- so it is a
@@ -331,9 +309,9 @@ class SegmentedStep:
             def f_menc():
                 with swap():
                     model.predict_motion_feat(batch, outputs)
-            menc.fwd, _ = capture(menc, f_menc, s_mot)
+            menc.fwd, _ = capture(menc, f_menc)
             self.segs.append(menc)
-            motion = _Segment("motion", s_dec)
+            motion = _Segment("motion", s_mot)
             dec_view = dict(outputs)
             for k, lst in list(outputs.items()):
                 if isinstance(k, tuple) and k[0] == "motion_feats":
@@ -350,7 +328,7 @@ class SegmentedStep:
             def f_motion():
                 with swap():
                     model.predict_motions(batch, dec_view, feats_done=True)
-            motion.fwd, _ = capture(motion, f_motion, s_dec)
+            motion.fwd, _ = capture(motion, f_motion)
             for k, v in dec_view.items():
                 if k not in outputs:
                     outputs[k] = v
@@ -390,20 +368,17 @@ class SegmentedStep:
         # The statistics-only passes feed nothing but the BatchNorm running buffers, which no training-mode kernel reads: their
         # fold (layers.DeferredStats, after the target-frame pass, in frame order) is a graph of its own, so that the side batch
         # -- twice the target pass's work -- need not finish before the loss; it runs on under the backward graphs and joins
-        # the step in front of the optimizer (DD_SEG_SIDE_LATE=0: joined in front of the loss as before).
+        # the step in front of the optimizer.
         self.fold_seg = None
-        if self.collectors and self.side_late:
+        if self.collectors:
             self.fold_seg = _Segment("fold", s_side)
 
             def f_fold():
                 for col in self.collectors:
                     col.apply()
-            self.fold_seg.fwd, _ = capture(self.fold_seg, f_fold, s_side)
+            self.fold_seg.fwd, _ = capture(self.fold_seg, f_fold)
 
         def f_loss():
-            if self.fold_seg is None:
-                for col in self.collectors:
-                    col.apply()
             # the loss path is fp32: half-precision network outputs are promoted here, inside the graph (Trainer.run_networks)
             once = {}                # one promotion per tensor: the two frames share their flow / mask tensors, and the loss checks identity
 
@@ -447,7 +422,7 @@ class SegmentedStep:
             self.loss_graphs = graphs
             lseg.fwd = None
         else:
-            lseg.fwd, _ = capture(lseg, f_loss, main)
+            lseg.fwd, _ = capture(lseg, f_loss)
             self.loss_graphs = [lseg.fwd]
         self.losses = {k: (v.detach() if torch.is_tensor(v) else v) for k, v in holder["losses"].items()}
         self._loss_grads = [(w, g) for w, g in zip(holder["wanted"], holder["grads"]) if g is not None]      # DD_SEG_CHECK
@@ -469,9 +444,7 @@ class SegmentedStep:
             else:
                 pairs = [(t, grad_of.get(id(leaves[id(t)]))) for t in seg.outs]
             pairs = [(t, g) for t, g in pairs if g is not None]
-            names = {"depth": ["depth_enc", "depth_dec"], "pose": ["pose_enc", "pose_dec"], "menc": ["motion_enc"],
-                     "motion": ["motion_dec", "motion_mask"], "side": []}[seg.name]
-            seg.params = [p for n in names for p in getattr(model, n).parameters() if p.requires_grad]
+            seg.params = [p for n in seg_names[seg.name] for p in getattr(model, n).parameters() if p.requires_grad]
             if not pairs or not seg.params:
                 seg.params = []
                 continue
@@ -495,14 +468,8 @@ class SegmentedStep:
                 grads = grads[:len(leaves_)]
                 dst = [v for v, g in zip(views, grads) if g is not None]
                 src = [g for g in grads if g is not None]
-                if "c" in dbg:
-                    for d_, s_ in zip(dst, src):
-                        d_.copy_(s_)
-                elif "n" not in dbg:
-                    torch._foreach_copy_(dst, src)
-                else:
-                    seg._keep = src
-            seg.bwd, _ = capture(seg, f_bwd, seg.stream, "bwd")
+                torch._foreach_copy_(dst, src)
+            seg.bwd, _ = capture(seg, f_bwd)
             seg.views = views
             for p, v in zip(seg.params, views):
                 p.grad = v
@@ -594,19 +561,6 @@ class SegmentedStep:
                 m.__dict__["_pending_batches"] += d * self.replays
         self.replays = 0
 
-    def run(self, inputs):
-        """One training step.  `inputs`: the batch on the device (after Trainer.upload_inputs).
-        DD_SEG_PRIORITY=1 (experiment): the caller's role -- inputs, depth net, loss, Adam: the critical path of the step -- is
-        replayed on a high-priority stream of its own, so that its kernels are dispatched ahead of the side branches'."""
-        if self.hp_stream is None:
-            return self._run(inputs)
-        caller = torch.cuda.current_stream()
-        self.hp_stream.wait_stream(caller)
-        with torch.cuda.stream(self.hp_stream):
-            out = self._run(inputs)
-        caller.wait_stream(self.hp_stream)
-        return out
-
     def _probe_reduce_mode(self):
         """DD_SEG_REDUCE=auto: which placement this replay uses, and -- once both have been timed -- the decision (one host sync and one
         small collective, once per captured step)."""
@@ -629,16 +583,13 @@ class SegmentedStep:
         self._probe_marks = None
         return self.reduce_mode
 
-    def _run(self, inputs):
+    def run(self, inputs):
+        """One training step.  `inputs`: the batch on the device (after Trainer.upload_inputs)."""
         tr = self.tr
         optimizer = tr.optim["optimizer"]
         if [grp["lr"] for grp in optimizer.param_groups] != self._lrs:
             self._capture_optimizer()           # the learning rate is a launch constant of the fused Adam kernel
         main = torch.cuda.current_stream()
-
-        def S(seg):
-            """The stream a segment is replayed on (DD_SEG_SERIAL=all | name,name: those on the caller's stream -- debugging)."""
-            return main if ("all" in self.serial or seg.name in self.serial) else seg.stream
         # the batch into the static buffers: one multi-tensor copy
         dst, src = [], []
         for k, v in self.static.items():
@@ -670,28 +621,15 @@ class SegmentedStep:
             """graph.replay() on the current stream; with DD_SEG_TIMING=1 between two timing events."""
             if graph is None:             # captured empty: nothing to launch
                 return
-            guard = self.exec_guard
-            if guard:
-                # one launch of a graph exec in flight at a time: wait (host) until the GPU has finished the previous step's
-                # launch of THIS graph before launching it again
-                last = self._last_launch.get(id(graph))
-                if last is not None:
-                    t = time.perf_counter()
-                    last.synchronize()
-                    self.host_wait_s += time.perf_counter() - t
-            cur = torch.cuda.current_stream()
             if not self.timing:
                 graph.replay()
             else:
+                cur = torch.cuda.current_stream()
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record(cur)
                 graph.replay()
                 e1.record(cur)
                 marks.append((seg.name + " " + what, e0, e1))
-            if guard:
-                done = torch.cuda.Event()
-                done.record(cur)
-                self._last_launch[id(graph)] = done
 
         if self.timing:
             self.t0 = torch.cuda.Event(enable_timing=True)
@@ -700,37 +638,28 @@ class SegmentedStep:
         side, pose, menc, motion, depth = self.side, self.pose, self.menc, self.motion, self.depth
         for seg in (side, pose, menc, motion):
             if seg is not None:
-                self._wait(S(seg), main)
+                self._wait(seg.stream, main)
         if menc is not None:                                 # the longest chain first: encoder -> decoders
-            with torch.cuda.stream(S(menc)):
+            with torch.cuda.stream(menc.stream):
                 replay(menc, menc.fwd, "fwd")
-        with torch.cuda.stream(S(pose)):
+        with torch.cuda.stream(pose.stream):
             replay(pose, pose.fwd, "fwd")
         if motion is not None:
-            self._wait(S(motion), S(pose))          # the decoders read the (detached) pose vectors ...
-            self._wait(S(motion), S(menc))          # ... and the encoder's features
-            with torch.cuda.stream(S(motion)):
+            self._wait(motion.stream, pose.stream)          # the decoders read the (detached) pose vectors ...
+            self._wait(motion.stream, menc.stream)          # ... and the encoder's features
+            with torch.cuda.stream(motion.stream):
                 replay(motion, motion.fwd, "fwd")
-        late = side is not None and self.fold_seg is not None
-        side_at = self.side_at if late else "start"
-
-        def run_side(behind):
-            """the side batch and the fold of its statistics, on the side batch's stream, behind `behind`"""
-            self._wait(S(side), behind)               # (the fold follows the target-frame pass's own update of the buffers)
-            with torch.cuda.stream(S(side)):
-                replay(side, side.fwd, "fwd")
-                replay(self.fold_seg, self.fold_seg.fwd, "fwd")
-        if side is not None and side_at == "start":
-            with torch.cuda.stream(S(side)):
+        if side is not None:
+            with torch.cuda.stream(side.stream):
                 replay(side, side.fwd, "fwd")
         replay(depth, depth.fwd, "fwd")
-        if late and side_at == "start":
-            self._wait(S(side), main)                   # the fold follows the target-frame pass's own update of the buffers
-            with torch.cuda.stream(S(side)):
+        if self.fold_seg is not None:
+            self._wait(side.stream, main)                   # the fold follows the target-frame pass's own update of the buffers
+            with torch.cuda.stream(side.stream):
                 replay(self.fold_seg, self.fold_seg.fwd, "fwd")
-        for seg in (None if late else side, pose, menc, motion):
+        for seg in (pose, menc, motion):
             if seg is not None:
-                self._wait(main, S(seg))
+                self._wait(main, seg.stream)
         if self.loss_events is not None:             # bench.py: HIP events around the whole loss, on the stream it runs on
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(main)
@@ -745,44 +674,41 @@ class SegmentedStep:
         # backward: the longest chain first (decoders, then the encoder behind them)
         works = []
         ran = []
-        if late and side_at == "loss":
-            run_side(main)
         if motion is not None and motion.bwd is not None:
-            self._wait(S(motion), main)
-            with torch.cuda.stream(S(motion)):
+            self._wait(motion.stream, main)
+            with torch.cuda.stream(motion.stream):
                 replay(motion, motion.bwd, "bwd")
                 if self.ddp and reduce_mode == "overlap":
                     works.append(self._all_reduce(motion))
             ran.append(motion)
         if menc is not None and menc.bwd is not None:
-            self._wait(S(menc), main)
-            self._wait(S(menc), S(motion))
-            with torch.cuda.stream(S(menc)):
+            self._wait(menc.stream, main)
+            self._wait(menc.stream, motion.stream)
+            with torch.cuda.stream(menc.stream):
                 replay(menc, menc.bwd, "bwd")
                 if self.ddp and reduce_mode == "overlap":
                     works.append(self._all_reduce(menc))
             ran.append(menc)
         if pose.bwd is not None:
-            self._wait(S(pose), main)
-            with torch.cuda.stream(S(pose)):
+            self._wait(pose.stream, main)
+            with torch.cuda.stream(pose.stream):
                 replay(pose, pose.bwd, "bwd")
                 if self.ddp and reduce_mode == "overlap":
                     works.append(self._all_reduce(pose))
             ran.append(pose)
-        if late and side_at == "pose":
-            run_side(S(pose))
         if depth.bwd is not None:
             replay(depth, depth.bwd, "bwd")
             if self.ddp and reduce_mode == "overlap":
                 works.append(self._all_reduce(depth))
-        for seg in ran + ([side] if late else []):
-            self._wait(main, S(seg))
-        if self.ddp and reduce_mode not in ("overlap", "none"):        # ("none": experiments with a one-rank group only)
+        for seg in ran + [side]:                # (the side batch and its fold ran on under the backward graphs)
+            if seg is not None:
+                self._wait(main, seg.stream)
+        if self.ddp and reduce_mode != "overlap":
             works.append(self._all_reduce(None))          # every backward graph has been joined: the whole buffer, one collective
         for w in works:
             if w is not None:
                 w.wait()                         # orders the collective before the optimizer on the current stream
-        if self.check or self.replays == self.check_at:
+        if self.check:
             self._check_finite("before the optimizer")
         if self.probe:
             self._probe()

@@ -322,6 +322,40 @@ def test_replayed_steps_stay_finite_with_the_host_ahead(monkeypatch):
         assert bool(torch.isfinite(p).all()), n
 
 
+REPLAY_ORDER = {
+    "fine_tune": ["inputs fwd", "menc fwd", "pose fwd", "motion fwd", "side fwd", "depth fwd", "fold fwd", "loss fwd",
+                  "motion bwd", "menc bwd", "pose bwd", "depth bwd", "optim optim"],
+    "disp_init": ["inputs fwd", "pose fwd", "side fwd", "depth fwd", "fold fwd", "loss fwd", "pose bwd", "depth bwd", "optim optim"],
+}
+
+
+@pytest.mark.parametrize("phase", ["fine_tune", "disp_init"])
+def test_replayed_step_launches_its_graphs_in_the_recorded_order(phase, monkeypatch):
+    """Which graphs a replayed step launches, in which host order (segments.SegmentedStep.run; DD_SEG_TIMING=1 brackets every launch
+    with events, timeline() names them).  The lists were recorded from the step as it stood before the placement switches of
+    rounds 3 and 4 were retired: a segment that is dropped, added or issued at another point of the step changes them."""
+    from Trainer import Trainer
+    from torch.utils.data import DataLoader
+    monkeypatch.setenv("DD_SEG_TIMING", "1")
+    torch.manual_seed(0)
+    opt = make_opt("litemono", ["--synthetic", "--hip_graph", "--multi_stream", "--channels_last", "--height", "96", "--width", "160"])
+    opt.batch_size = 2
+    tr = Trainer(opt)
+    tr.num_steps_per_epoch = 10
+    tr.setup_phase(phase)
+    tr.bool_automask = False
+    tr.step = 10
+    tr.set_train()
+    batch = next(iter(DataLoader(tr.get_dataset(["s {}".format(i) for i in range(2)]), batch_size=2)))
+    tr.upload_inputs(batch)
+    for _ in range(3):
+        tr.train_step(dict(batch))
+    assert tr._graph is not None and tr._graph.replays == 3
+    order = [name for name, _, _ in tr._graph.timeline()]
+    print(phase, order)
+    assert order == REPLAY_ORDER[phase]
+
+
 STOCK_SWITCHES = ("DD_STOCK_CONV_BIAS_GRAD", "DD_STOCK_REFLECT_PAD", "DD_STOCK_DWCONV", "DD_STOCK_LINEAR_GRAD", "DD_STOCK_BATCHNORM",
                   "DD_STOCK_XCA", "DD_STOCK_LAYERNORM", "DD_STOCK_CAT_CONV", "DD_STOCK_REDU_CAT", "DD_STOCK_LAYER_SCALE", "DD_STOCK_SLICES", "DD_STOCK_SMALL_CONV", "DD_STOCK_HEAD_CONV", "DD_STOCK_REDU", "DD_STOCK_MFMA_CONV", "DD_STOCK_MLP", "DD_STOCK_MLP_FUSED")
 
