@@ -188,9 +188,56 @@ __global__ void depth_metrics_mean_kernel(const float* __restrict__ per_sample, 
   mean[j] = acc / (float)B;
 }
 
+// Cross-batch totals of an evaluation, kept on the device.  One workgroup: thread l owns label l's eight slots, threads 0..8 also
+// own one slot of `totals` each.  Every slot is summed by one thread in batch order -- no atomics, no reduction across threads --
+// so the totals are identical from run to run and do not depend on how the dataset is cut into batches.
+constexpr int DM_ACC_NT = 256;
+
+__global__ __launch_bounds__(DM_ACC_NT) void depth_metrics_accumulate_kernel(const float* __restrict__ per_sample, const float* __restrict__ per_label,
+                                                                             int B, double* __restrict__ totals, double* __restrict__ label_totals) {
+  const int t = threadIdx.x;
+  if (t < 9) {
+    double acc = totals[t];
+    for (int b = 0; b < B; ++b) {
+      const bool kept = per_sample[b * 8 + 7] > 0.f;         // a sample without a kept LiDAR point carries a NaN row: counted, not summed
+      if (t < 7) {
+        if (kept) acc += (double)per_sample[b * 8 + t];
+      } else if (t == 7) {
+        acc += kept ? 1.0 : 0.0;
+      } else {
+        acc += kept ? 0.0 : 1.0;
+      }
+    }
+    totals[t] = acc;
+  }
+  if (per_label) {
+    double acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = label_totals[t * 8 + j];
+    for (int b = 0; b < B; ++b) {
+      const float* row = per_label + ((size_t)b * 256 + t) * 8;
+      const double cnt = (double)row[7];
+      if (!(cnt > 0.0)) continue;                            // a label the sample does not show: a zero row, nothing to add
+#pragma unroll
+      for (int j = 0; j < 7; ++j) acc[j] += (double)row[j] * cnt;       // err * cnt, as the reference tallies it (tools.py:70-71)
+      acc[7] += cnt;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) label_totals[t * 8 + j] = acc[j];
+  }
+}
+
 }  // namespace dd
 
 using namespace dd;
+
+extern "C" int dd_depth_metrics_accumulate(const float* per_sample, const float* per_label, int B, double* totals, double* label_totals,
+                                           void* stream) {
+  if (!per_sample || !totals || B < 1 || (per_label == nullptr) != (label_totals == nullptr)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(depth_metrics_accumulate_kernel, dim3(1), dim3(DM_ACC_NT), 0, static_cast<hipStream_t>(stream), per_sample, per_label, B,
+                     totals, label_totals);
+  return (int)hipGetLastError();
+}
 
 extern "C" size_t dd_depth_metrics_workspace_bytes(int B, int M) { return (size_t)B * 2 * M * sizeof(float); }
 extern "C" size_t dd_depth_metrics_masked_workspace_bytes(int B, int M) { return (size_t)B * 3 * M * sizeof(float); }

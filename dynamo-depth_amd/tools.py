@@ -6,7 +6,8 @@ GroundPlane, DepthMetrics, disp_to_depth, depth_to_disp, compute_smooth_loss, co
 Every differentiable operator is a torch.autograd.Function over the C ABI (hipops.functions); tensors must
 be on the GPU -- there is no CPU implementation of the loss path and none is silently substituted.
 (DepthMetrics is evaluation bookkeeping on gathered LiDAR hits and stays in plain torch.)
-MotionSegMetrics is the motion-mask evaluation of the reference's eval/motion_segmentation.py as an accumulating class.
+MotionSegMetrics is the motion-mask evaluation of the reference's eval/motion_segmentation.py as an accumulating class;
+DepthMetricsAccumulator and OdometryMetrics are the cross-batch bookkeeping of its eval/depth.py and eval/odometry.py, kept on the device.
 """
 import numpy as np
 import torch
@@ -308,3 +309,139 @@ class DepthMetrics(nn.Module):
         for m in names:
             metrics[m] = metrics[m] / disp_pred.size(0)
         return metrics
+
+
+class DepthMetricsAccumulator:
+    """DepthMetrics over a whole evaluation with the running totals on the device (the reference's eval/depth.py pulls seven scalars
+    to the host per batch; DepthMetrics' mask branch adds a torch.unique over the mask and two transfers).  update() is two launches on
+    the current stream -- dd_depth_metrics[_masked], then dd_depth_metrics_accumulate -- and returns nothing; compute() makes the one
+    transfer.  Every total is summed by one thread in batch order, so the result does not depend on the batch size (a ragged last
+    batch included).  GPU only: there is no torch fallback here."""
+
+    def __init__(self, img_bound, min_depth, max_depth):
+        import ctypes as C
+        self.depth_metric_names = ["de:abs_rel", "de:sq_rel", "de:rms", "de:log_rms", "da:a1", "da:a2", "da:a3"]
+        self.img_bound, self.min_depth, self.max_depth = img_bound, float(min_depth), float(max_depth)
+        self._bound = (C.c_double * 4)(*[float(v) for v in img_bound])
+        self.totals = self.label_totals = None
+        self._buf = None            # (device, B, M, masked) -> per_sample, mean, per_label, workspace
+
+    def reset(self):
+        self.totals = self.label_totals = None
+
+    def _buffers(self, dev, B, M, masked):
+        lib = L.load()
+        b = self._buf
+        if b is None or b["dev"] != dev or b["B"] < B or b["M"] < M or (masked and b["per_label"] is None):
+            cap_b, cap_m = max(B, b["B"] if b else 0), max(M, b["M"] if b else 0)
+            masked = masked or bool(b and b["per_label"] is not None)
+            nbytes = int(lib.dd_depth_metrics_masked_workspace_bytes(cap_b, cap_m))          # the larger of the two workspaces
+            b = self._buf = {"dev": dev, "B": cap_b, "M": cap_m, "ws_bytes": nbytes,
+                             "per_sample": torch.empty((cap_b, 8), dtype=torch.float32, device=dev),
+                             "mean": torch.empty(7, dtype=torch.float32, device=dev),
+                             "per_label": torch.empty((cap_b, 256, 8), dtype=torch.float32, device=dev) if masked else None,
+                             "ws": HF._ws(nbytes, dev)}
+        return b
+
+    def update(self, inputs, disp_scaled, mask=None):
+        """inputs: the loader's depth_gt (B,M,3), depth_valid (B,M), gt_dim (B,2); disp_scaled (B,1,H,W) = outputs['disp_scaled',0,0];
+        mask (B,h,w) integer labels below 256 in ground-truth pixels, or None."""
+        from hipops import abi
+        lib = L.load()
+        disp = HF._dev(disp_scaled.detach(), "disp_scaled")
+        dev = disp.device
+        B, _, H, W = disp.shape
+        lidar = inputs["depth_gt"].to(dev, torch.float32).contiguous()
+        valid = inputs["depth_valid"].to(dev, torch.float32).contiguous()
+        dims = inputs["gt_dim"].to(dev, torch.int32).contiguous()
+        M = lidar.shape[1]
+        masked = mask is not None
+        if masked and (mask.dim() != 3 or mask.shape[0] != B or mask.is_floating_point()):
+            raise ValueError("DepthMetricsAccumulator.update: mask must be (B,h,w) integer labels, got {} {}".format(tuple(mask.shape), mask.dtype))
+        if self.totals is None:
+            self.totals = torch.zeros(9, dtype=torch.float64, device=dev)
+        if masked and self.label_totals is None:
+            self.label_totals = torch.zeros((256, 8), dtype=torch.float64, device=dev)
+        b = self._buffers(dev, B, M, masked)
+        stream = L.current_stream()
+        if masked:
+            m8 = mask.to(dev, torch.uint8).contiguous()
+            L.check(lib.dd_depth_metrics_masked(abi.ptr(disp), B, H, W, abi.ptr(lidar), abi.ptr(valid), M, abi.ptr(dims), self._bound, self.min_depth,
+                                                self.max_depth, abi.ptr(m8), m8.shape[1], m8.shape[2], abi.ptr(b["per_sample"]), abi.ptr(b["mean"]),
+                                                abi.ptr(b["per_label"]), abi.ptr(b["ws"]), b["ws_bytes"], stream), "dd_depth_metrics_masked")
+        else:
+            L.check(lib.dd_depth_metrics(abi.ptr(disp), B, H, W, abi.ptr(lidar), abi.ptr(valid), M, abi.ptr(dims), self._bound, self.min_depth,
+                                         self.max_depth, abi.ptr(b["per_sample"]), abi.ptr(b["mean"]), abi.ptr(b["ws"]), b["ws_bytes"], stream),
+                    "dd_depth_metrics")
+        L.check(lib.dd_depth_metrics_accumulate(abi.ptr(b["per_sample"]), abi.ptr(b["per_label"]) if masked else None, B, abi.ptr(self.totals),
+                                                abi.ptr(self.label_totals) if masked else None, stream), "dd_depth_metrics_accumulate")
+
+    def compute(self):
+        if self.totals is None:
+            raise RuntimeError("DepthMetricsAccumulator.compute() before any update()")
+        names = self.depth_metric_names
+        both = torch.cat([self.totals] + ([self.label_totals.reshape(-1)] if self.label_totals is not None else [])).cpu().numpy()      # the one transfer
+        totals = both[:9]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = {"overall": {m: float(totals[j] / totals[7]) for j, m in enumerate(names)}, "num": int(totals[7]), "skipped": int(totals[8])}
+        if self.label_totals is not None:
+            lt = both[9:].reshape(256, 8)
+            out["by_label"] = {l: {m: float(lt[l, j] / lt[l, 7]) for j, m in enumerate(names)} for l in range(256) if lt[l, 7] > 0}
+            out["label_counts"] = {l: int(lt[l, 7]) for l in range(256) if lt[l, 7] > 0}
+        return out
+
+
+class OdometryMetrics:
+    """Absolute trajectory error and ground-truth speed over `track_length`-frame snippets (reference eval/odometry.py:19-41,70-96), one
+    dd_odom_snippets launch per segment into a growing device buffer; nothing returns to the host before compute().  A segment of N frame
+    pairs yields S = snippet_count(N) snippets, the last of them one point shorter than the others -- the reference's behaviour."""
+
+    def __init__(self, track_length=5):
+        if not 2 <= int(track_length) <= 16:
+            raise ValueError("OdometryMetrics: 2 <= track_length <= 16, got {}".format(track_length))
+        self.track_length = int(track_length)
+        self.values = None          # (2, capacity) float64 on the device: ates, speeds
+        self.used = 0
+        self.segments = []          # (offset, S) per add_segment
+
+    def snippet_count(self, N):
+        """S of a segment with N frame pairs (dd_odom_snippet_count restated; -1 for N < 1)."""
+        return -1 if N < 1 else max(0, min(N, N - self.track_length + 3))
+
+    def reset(self):
+        self.values, self.used, self.segments = None, 0, []
+
+    def add_segment(self, pred_T, gt_global):
+        """pred_T (N,4,4) fp32 on the device; gt_global (N+1, 3 or 4, 4) float64 (numpy or tensor), uploaded once."""
+        from hipops import abi
+        lib = L.load()
+        pred = HF._dev(pred_T.detach(), "pred_T")
+        if pred.dim() != 3 or tuple(pred.shape[1:]) != (4, 4) or pred.shape[0] < 1:
+            raise ValueError("OdometryMetrics.add_segment: pred_T must be (N,4,4) with N >= 1, got {}".format(tuple(pred.shape)))
+        N = pred.shape[0]
+        gt = torch.as_tensor(gt_global, dtype=torch.float64)
+        if gt.dim() != 3 or gt.shape[0] != N + 1 or gt.shape[1] not in (3, 4) or gt.shape[2] != 4:
+            raise ValueError("OdometryMetrics.add_segment: gt_global must be (N+1, 3 or 4, 4) for N = {}, got {}".format(N, tuple(gt.shape)))
+        if gt.shape[1] == 3:
+            last = torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64, device=gt.device).expand(N + 1, 1, 4)
+            gt = torch.cat((gt, last), 1)
+        gt = gt.to(pred.device).contiguous()
+        S = int(lib.dd_odom_snippet_count(N, self.track_length))
+        if self.values is None or self.used + S > self.values.shape[1]:
+            grown = torch.zeros((2, max(2 * (self.used + S), 1024)), dtype=torch.float64, device=pred.device)
+            if self.values is not None:
+                grown[:, :self.used] = self.values[:, :self.used]
+            self.values = grown
+        ate, speed = self.values[0, self.used:], self.values[1, self.used:]
+        L.check(lib.dd_odom_snippets(abi.ptr(pred), abi.ptr(gt), N, self.track_length, abi.ptr(ate) if S else None, abi.ptr(speed) if S else None,
+                                     L.current_stream()), "dd_odom_snippets")
+        self.segments.append((self.used, S))
+        self.used += S
+
+    def compute(self):
+        """{'ates', 'speeds': float64 numpy arrays over all snippets, 'segments': [(ates, speeds) slice per add_segment]}: one transfer."""
+        if self.values is None:
+            raise RuntimeError("OdometryMetrics.compute() before any add_segment()")
+        both = self.values[:, :self.used].cpu().numpy()
+        ates, speeds = both[0].copy(), both[1].copy()
+        return {"ates": ates, "speeds": speeds, "segments": [(ates[o:o + s], speeds[o:o + s]) for o, s in self.segments]}

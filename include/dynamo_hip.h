@@ -382,6 +382,30 @@ int dd_depth_metrics_masked(const float* disp, int B, int H, int W, const float*
                             const double* img_bound, float min_depth, float max_depth, const uint8_t* mask, int mask_h, int mask_w,
                             float* per_sample, float* mean, float* per_label, void* workspace, size_t workspace_bytes, void* stream);
 size_t dd_depth_metrics_masked_workspace_bytes(int B, int M);
+/* Cross-batch totals of a depth evaluation, kept on the device (the reference's eval/depth.py pulls seven scalars to the host per batch).
+ * per_sample [B,8] as dd_depth_metrics writes it; per_label [B,256,8] as dd_depth_metrics_masked writes it, or NULL.
+ * totals [9] doubles, ACCUMULATED into: [0..6] += (double)per_sample[b][j] over the samples with per_sample[b][7] > 0, in batch order;
+ * [7] += the number of such samples; [8] += the number of samples without a kept LiDAR point (their NaN rows are not summed).
+ * label_totals [256,8] doubles, ACCUMULATED into (NULL iff per_label is NULL): [l][j<7] += (double)per_label[b][l][j] * (double)per_label[b][l][7],
+ * [l][7] += per_label[b][l][7], in batch order.  The caller zeroes both once per evaluation (as dd_motion_pr's counts).
+ * One workgroup of 256 threads, every slot summed by one thread: no atomics, no reduction across threads -- the totals are identical
+ * from run to run and independent of how the dataset is cut into batches.
+ * hipErrorInvalidValue, nothing launched: per_sample or totals NULL, B < 1, exactly one of per_label / label_totals NULL. */
+int dd_depth_metrics_accumulate(const float* per_sample, const float* per_label, int B, double* totals, double* label_totals, void* stream);
+
+/* The reference's odometry evaluation behind the network (eval/odometry.py:19-41,70-96), in float64 on the device.
+ * pred (N,4,4) fp32: transformation_from_parameters(axisangle, translation) of the frame pairs (0 -> +1), widened on load;
+ * gt_global (N+1,4,4) float64 global camera poses, affine (last row 0 0 0 1).
+ * Snippet i = 0 .. S-1 has P = min(track_length-1, N-i) + 1 points: the translations of the running product I.T_i.T_{i+1}... with the
+ * axes reordered (z, x, y), against the same running product over the local poses inv(inv(G[k-1]).G[k]).
+ * ate[i] = sqrt(sum |scale.pred - gt|^2) / P after aligning the first points, scale = sum(gt.pred) / sum(pred^2), unguarded: an all-zero
+ * prediction gives NaN as in the reference.  speed[i] = mean distance between consecutive ground-truth points.
+ * A snippet is kept iff P >= track_length - 1, so S = dd_odom_snippet_count(N, track_length) = max(0, min(N, N - track_length + 3)) and
+ * the LAST kept snippet is one point shorter than the others (the reference's behaviour, reproduced).
+ * One thread per snippet; S == 0 returns success without a launch.  hipErrorInvalidValue (dd_odom_snippet_count: -1) for
+ * track_length outside [2, 16] or N < 1; hipErrorInvalidValue for a NULL pointer with S > 0. */
+int dd_odom_snippet_count(int N, int track_length);
+int dd_odom_snippets(const float* pred, const double* gt_global, int N, int track_length, double* ate, double* speed, void* stream);
 
 /* Motion-segmentation precision/recall counts in one pass (reference eval/motion_segmentation.py:52-95,118-140: the
  * (B, T, H, W) `pred_mask > thrds` scan with its three sums per sample, and the second walk over the dataset for the
