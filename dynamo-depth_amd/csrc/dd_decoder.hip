@@ -20,7 +20,22 @@ namespace dd {
 
 constexpr int DEC_NT = 256;
 
-__device__ __forceinline__ float elu1(float v) { return v <= 0.f ? expf(v) - 1.f : v; }          // alpha = 1 (nn.ELU default)
+// alpha = 1 (nn.ELU default).  ATen's ELU is expm1: expf(v) - 1.f is off by up to 2^-24 ABSOLUTE, a few percent of the value at v = -1e-6
+// and all of it at -2^-126.  Above -1/4: v (1 + v h(v)), h the degree-3 least-squares fit of (expm1(v) / v - 1) / v on Chebyshev
+// nodes of [-1/4, 0] (fit error 2^-28 of the value; in fp32 within 1.6 x 2^-24 of expm1, and exactly v where v^2 vanishes).  At
+// and below -1/4 |expm1(v)| >= 0.22, and exp2(v log2 e) - 1 carries |v| e^v 2^-24 <= 0.37 x 2^-24 from the rounded argument and one
+// ulp (2^-24 below 1) from v_exp_f32: within 6.2 x 2^-24 of the value.  Both sides are computed and one is selected: the lanes of
+// a wave do not agree on the side, and the bilinear mode evaluates this sixteen times per thread -- the library's expm1f and a
+// version with expf each made that kernel a fifth slower (profiles/glue_parity.txt); this one has fewer instructions than
+// expf(v) - 1.f had.
+__device__ __forceinline__ float elu1(float v) {
+  float h = 0x1.ed9a98p-8f;
+  h = fmaf(h, v, 0x1.53f994p-5f);
+  h = fmaf(h, v, 0x1.554e28p-3f);
+  h = fmaf(h, v, 0x1.ffffe8p-2f);
+  const float near0 = v * fmaf(h, v, 1.f), far = __expf(v) - 1.f;
+  return v > 0.f ? v : (v > -0.25f ? near0 : far);
+}
 __device__ __forceinline__ float elu1_grad(float v) { return v <= 0.f ? expf(v) : 1.f; }
 template <bool ELU>
 __device__ __forceinline__ float4 act4(float4 v) {
@@ -181,9 +196,10 @@ static void up_cat_pad_bwd_launch(const void* g_, const void* x_, int B, int h, 
 using namespace dd;
 
 static bool up_cat_pad_ok(const void* x, int B, int h, int w, int C1, int C2, int mode, int dtype) {
-  const int H = mode == 2 ? h : 2 * h;
-  return x && B >= 1 && B <= 65535 && h >= 2 && w >= 2 && H >= 4 && H + 2 <= 65535 && C1 >= 4 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 && mode >= 0 &&
-         mode <= 2 && dtype >= 0 && dtype <= 2;
+  // H, W >= 4 as dd_reflect_pad1_nhwc_t: at W = 3 column 1 is mirrored by both padded borders and pad_fold has one mirror slot
+  const int H = mode == 2 ? h : 2 * h, W = mode == 2 ? w : 2 * w;
+  return x && B >= 1 && B <= 65535 && h >= 2 && w >= 2 && H >= 4 && W >= 4 && H + 2 <= 65535 && C1 >= 4 && C1 % 4 == 0 && C2 >= 0 && C2 % 4 == 0 &&
+         mode >= 0 && mode <= 2 && dtype >= 0 && dtype <= 2;
 }
 
 extern "C" int dd_up_cat_pad_t(const void* x, const void* skip, int B, int h, int w, int C1, int C2, int mode, int elu, void* out, int dtype,

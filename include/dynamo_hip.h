@@ -475,7 +475,8 @@ int dd_reflect_pad1_nhwc_bwd_t(const void* g_out, int B, int H, int W, int C, vo
  * up (mode): 0 nearest x2 (F.interpolate(scale_factor=2, mode="nearest")), 1 bilinear x2 (mode="bilinear", align_corners=False),
  * 2 none (H,W = h,w: ELU + padding only); skip: (B,H,W,C2) or NULL with C2 = 0.  C1, C2 multiples of 4.
  * *_bwd: g_out (B,H+2,W+2,C1+C2) -> g_x (B,h,w,C1) (times ELU'(x) when elu) and g_skip (B,H,W,C2); either may be NULL; gather
- * form, no atomics, overwritten.  dtype: DD_DTYPE_*. */
+ * form, no atomics, overwritten.  dtype: DD_DTYPE_*.  h, w >= 2 and H, W >= 4 (mode 2: h, w >= 4, as dd_reflect_pad1_nhwc_t), anything
+ * smaller returns hipErrorInvalidValue and launches nothing.  ELU is expm1(x) for x <= 0 as ATen's, to within 7 x 2^-24 of the value. */
 int dd_up_cat_pad_t(const void* x, const void* skip, int B, int h, int w, int C1, int C2, int mode, int elu, void* out, int dtype, void* stream);
 int dd_up_cat_pad_bwd_t(const void* g_out, const void* x, int B, int h, int w, int C1, int C2, int mode, int elu, void* g_x, void* g_skip,
                         int dtype, void* stream);
