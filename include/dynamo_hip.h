@@ -369,7 +369,10 @@ int dd_pack_rgb(const float* planar, int B, int H, int W, float* packed, void* s
  * valid [B,M] floats (0 = padding); gt_dim [B,2] int32 (height, width) on the DEVICE; img_bound: 4 doubles on the HOST
  * (opt.eval_img_bound: up, down, left, right fractions). per_sample [B,8] = abs_rel, sq_rel, rms, log_rms, a1, a2, a3,
  * kept-point count; mean [7] = batch mean as the reference returns it. A sample with no kept point yields NaNs (the
- * reference raises). workspace: dd_depth_metrics_workspace_bytes(B, M). One workgroup per sample, no host sync. */
+ * reference raises). workspace: dd_depth_metrics_workspace_bytes(B, M). One workgroup per sample, no host sync.
+ * Workspace layout (what the kernel leaves there): per sample M floats of ground truth, M floats of predicted depth, and in the
+ * masked call M int32 labels. Dropped points carry -1 in the first two (their label slot is not written).
+ * hipErrorInvalidValue, nothing launched: a NULL pointer, B, H, W or M < 1 (masked: mask_h or mask_w < 1), a workspace too small. */
 int dd_depth_metrics(const float* disp, int B, int H, int W, const float* lidar, const float* valid, int M, const int* gt_dim,
                      const double* img_bound, float min_depth, float max_depth, float* per_sample, float* mean,
                      void* workspace, size_t workspace_bytes, void* stream);
@@ -377,7 +380,8 @@ size_t dd_depth_metrics_workspace_bytes(int B, int M);
 /* The mask branch of tools.DepthMetrics.forward (tools.py:23-25,58-72): `mask` (B,mask_h,mask_w) uint8 labels in ground-truth pixels
  * (the loaders' sem_mask / mot_mask).  per_label [B,256,8] = for every label that occurs among a sample's kept LiDAR points, the seven
  * errors over those points and their count (zero rows otherwise); the caller forms sum_b err*cnt and sum_b cnt per label.
- * workspace: dd_depth_metrics_masked_workspace_bytes(B, M). */
+ * A mask smaller than the ground truth: a point outside it carries label 0.
+ * workspace: dd_depth_metrics_masked_workspace_bytes(B, M), laid out as above with the labels as the third block of every sample. */
 int dd_depth_metrics_masked(const float* disp, int B, int H, int W, const float* lidar, const float* valid, int M, const int* gt_dim,
                             const double* img_bound, float min_depth, float max_depth, const uint8_t* mask, int mask_h, int mask_w,
                             float* per_sample, float* mean, float* per_label, void* workspace, size_t workspace_bytes, void* stream);
