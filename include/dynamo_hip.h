@@ -439,6 +439,25 @@ int dd_motion_pr(const float* pred, int B, int h, int w, const uint8_t* mot, con
 int dd_fill_contours(const int16_t* vertices, int v_cap, const int32_t* contours, int c_cap, int B, int H, int W, uint8_t* mask,
                      void* stream);
 
+/* KITTI LiDAR depth lists (reference prepare_data/kitti.py:104-115 with kitti_util.py generate_depth_map(..., vel_depth=True)): every
+ * scan of a batch projected through every camera matrix, z-buffered with the reference's duplicate rule, and the positive pixels
+ * written as row-major [r, c, d] rows; DESIGN 4.18 holds the definition, hipops/lidar.py depth_points_host restates it in numpy.
+ * points (n_total,4) float32, 16-byte aligned, column 3 ignored: scan s is rows offsets[s] .. offsets[s+1]-1.
+ * offsets [S+1] int32 on the HOST (read and validated before anything is launched, not held past return): offsets[0] == 0,
+ *   non-decreasing, offsets[S] == n_total.
+ * P (C,3,4) float64 on the device, one matrix per camera, shared by the batch.  Job (s,c) = scan s through P[c], an H x W image.
+ * counts [S*C] int32: counts[s*C+c] = rows of job (s,c); every count is written.
+ * rows (C*n_total,3) float64: job (s,c) owns the rows C*offsets[s] + c*n_s .. + n_s - 1 (n_s = offsets[s+1]-offsets[s]) and writes the
+ *   first counts[s*C+c] of them (a job has at most one row per point); the rest of its segment is left as it was.
+ * maps NULL or (S,C,H,W) float32: the dense map of every job, every element written.
+ * workspace: dd_lidar_depth_points_workspace_bytes(S, C, H, W), 4-byte aligned; initialised on the stream by the call.
+ * Integer min/max atomics only: every output byte is the same from run to run.  4 launches and one memset per 16 scans.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer (maps excepted), S < 1, C < 1 or > 65535, H < 1, W < 2, H*W or n_total
+ * above 2^31-1, offsets that decrease or do not run from 0 to n_total, a workspace that is too small, a misaligned pointer. */
+size_t dd_lidar_depth_points_workspace_bytes(int S, int C, int H, int W);
+int dd_lidar_depth_points(const float* points, long long n_total, const int32_t* offsets, int S, const double* P, int C, int H, int W,
+                          int32_t* counts, double* rows, float* maps, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
  * bn2(+identity)->relu as used by networks/resnet_encoder.py:42-88, the stem bn1->relu, and LiteMono's BNGELU / DilatedConv.bn1
