@@ -239,6 +239,10 @@ def declare(lib):
         "dd_mlp_fwd": (i, [v, v, v, v, v, i, i, v, v]),
         "dd_pw_gemm": (i, [v, v, v, i, i, i, i, v, v]),
         "dd_gelu_pair": (i, [v, v, v, z, v]),
+        "dd_linear_wgrad_supported": (i, [i, i, i]),
+        "dd_linear_wgrad_workspace_bytes": (z, [i, i, i]),
+        "dd_linear_wgrad": (i, [v, v, i, i, i, v, v, v, z, v]),
+        "dd_linear_wgrad_n": (i, [v, v, i, i, i, i, v, v, v, z, v]),
         "dd_adam_chunk": (i, []),
         "dd_adam_multi": (i, [v, i, v, i, v, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, v, v, v]),
         "dd_error_string": (C.c_char_p, [i]),
@@ -277,6 +281,7 @@ EXPORTED = (
     "dd_conv3x3_half_supported", "dd_conv3x3_half_pack_bytes", "dd_conv3x3_half_pack", "dd_conv3x3_half",
     "dd_conv3x3_half_wgrad_workspace_bytes", "dd_conv3x3_half_bwd_weight",
     "dd_pw_gemm_pack_bytes", "dd_mlp_pack", "dd_pw_gemm", "dd_gelu_pair", "dd_mlp_fwd_supported", "dd_mlp_fwd",
+    "dd_linear_wgrad_supported", "dd_linear_wgrad_workspace_bytes", "dd_linear_wgrad", "dd_linear_wgrad_n",
     "dd_error_string", "dd_abi_version",
 )
 

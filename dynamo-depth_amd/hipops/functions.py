@@ -70,6 +70,52 @@ def _wgrad_1x1(go, x, w, B, H, W):
     return gw.reshape(cout, cin)
 
 
+_LINEAR_WGRAD_CALLS = [0]
+
+
+def linear_wgrad_calls():
+    """How many times dd_linear_wgrad has served a Linear's weight (+ bias) gradient in this process."""
+    return _LINEAR_WGRAD_CALLS[0]
+
+
+def _linear_wgrad_gate(M, cout, cin):
+    """The shapes at which dd_linear_wgrad measured ahead of the library path (MIOpen's 1x1 weight gradient + its zeroing launch + the
+    two launches of the column sum) on MI355X -- profiles/linear_wgrad.txt, scripts/time_linear_wgrad.py: every row of that table.
+    The channel bounds are the table's extent (8 to 1 344 channels, results up to 1344 x 224; aspect ratios 1:1, 1:3, 1:6 either way and
+    300 x 8 were timed, others inside the bounds are taken on their strength), not a crossover: nothing larger was measured.  M is
+    deliberately open: both paths stream the rows, and the table's 15 to 92 160 rows show the lead at either end -- at few rows the
+    library's four launches (and, below its split-K records, 70-130 us kernels) against two, at many rows one read of g against two."""
+    return min(cout, cin) >= 8 and cout * cin <= 1344 * 224
+
+
+def linear_wgrad_ok(g, x, cout, cin):
+    """dd_linear_wgrad takes this weight gradient: fp32 operands, dense 2-D views, a supported and gated shape, no DD_STOCK_LINEAR_WGRAD=1."""
+    if os.environ.get("DD_STOCK_LINEAR_WGRAD", "0") == "1" or g.dtype != torch.float32 or x.dtype != torch.float32:
+        return False
+    M = g.numel() // cout
+    return bool(g.is_cuda and g.is_contiguous() and x.is_contiguous() and x.numel() == M * cin and _linear_wgrad_gate(M, cout, cin)
+                and L.load().dd_linear_wgrad_supported(M, cout, cin))
+
+
+def _linear_param_grads(g, x, w, B, H, W, need_w, need_b, stream):
+    """(gw, gb) of a Linear over the channel axis, None where not needed: g (B*H*W, cout) and x (B*H*W, cin) -> (cout, cin) and fp32
+    (cout,).  One pass of dd_linear_wgrad over both operands where linear_wgrad_ok holds; else the library's 1x1 weight gradient and
+    the fixed-order column sum, as before."""
+    cout, cin = w.shape
+    M = B * H * W
+    if need_w and linear_wgrad_ok(g, x, cout, cin):
+        gw = torch.empty((cout, cin), dtype=torch.float32, device=g.device)
+        gb = torch.empty(cout, dtype=torch.float32, device=g.device) if need_b else None
+        nbytes = _ws_bytes("dd_linear_wgrad_workspace_bytes", M, cout, cin)
+        ws = _ws(nbytes, g.device)
+        L.check(L.load().dd_linear_wgrad_n(_p(g), _p(x), M, cout, cin, mfma_products(), _p(gw), _p(gb), _p(ws), nbytes, stream), "dd_linear_wgrad_n")
+        _LINEAR_WGRAD_CALLS[0] += 1
+        return gw, gb
+    gw = _wgrad_1x1(g, x, w, B, H, W) if need_w else None
+    gb = _channel_sum(g, M, cout, DTYPE_CODE[g.dtype], stream) if need_b else None
+    return gw, gb
+
+
 def _wgrad_3x3_library(g, x, w_like, pad):
     """The library's weight gradient of a 3x3 stride-1 convolution (only the shape, type and layout of w_like are read)."""
     return torch.ops.aten.convolution_backward(g, x, w_like, None, (1, 1), (pad, pad), (1, 1), False, [0, 0], 1, (False, True, False))[1]
@@ -859,8 +905,11 @@ def depthwise_conv3x3(x, weight, dilation):
 class PointwiseLinearFn(torch.autograd.Function):
     """nn.Linear over the channel axis of a channels-last (B,H,W,Cin) tensor (LiteMono's pwconv1/pwconv2, reference
     networks/depth_encoder.py:200-203). Forward and data gradient are the plain GEMMs; the weight gradient -- a (Cout x Cin)
-    result reduced over B*H*W = 92160 rows, which the BLAS back-end runs at 17 TFLOP/s without split-K -- goes through MIOpen's
-    1x1 weight-gradient implicit GEMM (5x faster here), and the bias gradient through the fixed-order HIP column sum.
+    result reduced over B*H*W = 92160 rows, which the BLAS back-end runs at 17 TFLOP/s without split-K -- and the bias gradient come
+    from ONE pass of dd_linear_wgrad over g and x (csrc/dd_linear_wgrad.hip: three bf16 pieces per fp32 operand on the matrix pipe,
+    per-workgroup partials folded in a fixed order, bit-reproducible) where linear_wgrad_ok holds.  Elsewhere -- half types under
+    autocast, shapes outside _linear_wgrad_gate, DD_STOCK_LINEAR_WGRAD=1 -- the weight gradient is MIOpen's 1x1 weight-gradient
+    implicit GEMM (5x faster than the BLAS here) and the bias gradient the fixed-order HIP column sum.
     x, weight and bias arrive in ONE dtype (under autocast the caller hands over the half-precision casts)."""
 
     @staticmethod
@@ -879,10 +928,9 @@ class PointwiseLinearFn(torch.autograd.Function):
         gx = gw = gb = None
         if ctx.needs_input_grad[0]:
             gx = torch.mm(g.view(-1, cout), weight).view(B, H, W, cin)
-        if ctx.needs_input_grad[1]:
-            gw = _wgrad_1x1(g, x, weight, B, H, W)
-        if ctx.needs_input_grad[2]:
-            gb = _channel_sum(g, B * H * W, cout, DTYPE_CODE[g.dtype], L.current_stream()).to(weight.dtype)
+        gw, gb = _linear_param_grads(g, x, weight, B, H, W, ctx.needs_input_grad[1], ctx.needs_input_grad[2], L.current_stream())
+        if gb is not None:
+            gb = gb.to(weight.dtype)
         return gx, gw, gb
 
 
@@ -928,11 +976,8 @@ def mlp_ok(y, block):
 def _mlp_param_grads(needs, g, gpre, y, post, w1, w2, B, H, W, stream):
     """(gw1, gb1, gw2, gb2) of an MLP block once dd_gelu_pair has run, launched in that order, None where needs_input_grad does not ask.
     g: the block's output gradient, gpre: the pre-activation's, post = GELU(pre), y: the block's input -- B*H*W rows each."""
-    M, code = B * H * W, DTYPE_CODE[torch.float32]
-    gw1 = _wgrad_1x1(gpre, y, w1, B, H, W) if needs[1] else None
-    gb1 = _channel_sum(gpre, M, w1.shape[0], code, stream) if needs[2] else None
-    gw2 = _wgrad_1x1(g, post, w2, B, H, W) if needs[3] else None
-    gb2 = _channel_sum(g, M, w2.shape[0], code, stream) if needs[4] else None
+    gw1, gb1 = _linear_param_grads(gpre, y, w1, B, H, W, needs[1], needs[2], stream)
+    gw2, gb2 = _linear_param_grads(g, post, w2, B, H, W, needs[3], needs[4], stream)
     return gw1, gb1, gw2, gb2
 
 
@@ -941,8 +986,8 @@ class MlpFn(torch.autograd.Function):
     channels-last (B,H,W,C) tensor through dd_pw_gemm (csrc/dd_pw_gemm.hip): both Linears and both data gradients on the bf16 matrix
     pipe from three bf16 pieces per fp32 operand (fp32 accuracy, bit-reproducible); the GELU is applied to the second Linear's operand
     while it is split, so the activated 6C-wide tensor is neither written nor read in the forward.  The backward rebuilds it together
-    with the activation's gradient in ONE pass (dd_gelu_pair); the weight gradients go through MIOpen's 1x1 weight-gradient implicit
-    GEMM and the bias gradients through the fixed-order HIP column sum, as in PointwiseLinearFn."""
+    with the activation's gradient in ONE pass (dd_gelu_pair); the weight and bias gradients of both Linears are
+    _linear_param_grads' (dd_linear_wgrad: one pass per Linear), as in PointwiseLinearFn."""
 
     @staticmethod
     def forward(ctx, y, w1, b1, w2, b2):

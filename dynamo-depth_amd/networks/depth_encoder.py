@@ -114,7 +114,7 @@ class XCA(nn.Module):
     @staticmethod
     def _linear(layer, x, hw):
         """layer(x) for tokens (B,N,C); with the (H,W) of the token grid known, through the channels-last Linear whose weight
-        gradient runs as MIOpen's 1x1 wrw (K = B*N = 92 160 rows against a 64 x 192 result: 300 us as a plain GEMM)."""
+        and bias gradient come from one pass of dd_linear_wgrad (K = B*N = 92 160 rows against a 64 x 192 result: 300 us as a plain GEMM)."""
         if hw is not None and x.is_cuda and layer.bias is not None and os.environ.get("DD_STOCK_LINEAR_GRAD", "0") != "1":
             from hipops.functions import pointwise_linear
             B, N, Cc = x.shape
@@ -231,7 +231,7 @@ def _mlp_residual(block, y, res):
             y = mlp_recompute(y, block)                        # training pass: the same kernel forward, the hidden tensor rebuilt in the backward
         elif mlp_ok(y, block):
             y = mlp(y, block)                                  # csrc/dd_pw_gemm.hip: both Linears on the bf16 matrix pipe (fp32 accuracy), GELU in the second one's prologue
-        else:                                                  # weight gradient through MIOpen's 1x1 wrw, bias gradient in HIP
+        else:                                                  # weight + bias gradient: one pass of dd_linear_wgrad
             y = pointwise_linear(block.act(pointwise_linear(y, block.pwconv1)), block.pwconv2)
     else:
         y = block.pwconv2(block.act(block.pwconv1(y.reshape(-1, Cc)))).reshape(B, H, W, Cc)

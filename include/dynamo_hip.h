@@ -682,6 +682,21 @@ int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fuse
 int dd_pw_gemm(const float* x, const void* pack, const float* bias, int M, int K, int N, int gelu_in, float* y, void* stream);
 int dd_gelu_pair(const float* pre, float* g_inout, float* post, size_t n, void* stream);
 
+/* Weight AND bias gradient of those Linears, and of XCA's qkv / proj (reference networks/depth_encoder.py:200-203, :58-60), in one pass over
+ * their operands (csrc/dd_linear_wgrad.hip): g_weight (cout,cin) = g_out^T . x and g_bias (cout) = the column sums of g_out, from the dense
+ * row-major fp32 matrices g_out (M,cout) and x (M,cin) (any float alignment: the kernel loads dwords), each read ONCE; the rows are the
+ * contraction, with the split arithmetic of dd_conv3x3_mfma_bwd_weight (`products` of the _n form: 6 / 3 / 1 as there).
+ * dd_linear_wgrad_supported: M >= 1, cout % 4 == cin % 4 == 0, 4 <= cout, cin <= 8192, and M * max(cout, cin) < 2^30 (the kernel addresses
+ * both matrices with 32-bit byte offsets).  workspace: dd_linear_wgrad_workspace_bytes(M, cout, cin) bytes, private to the call's stream -- one partial
+ * per workgroup, folded in a fixed order by a second launch that writes every element of both results: no atomics, no zero-fill,
+ * bit-reproducible.  g_bias may be NULL. */
+int dd_linear_wgrad_supported(int M, int cout, int cin);
+size_t dd_linear_wgrad_workspace_bytes(int M, int cout, int cin);
+int dd_linear_wgrad(const float* g_out, const float* x, int M, int cout, int cin, float* g_weight, float* g_bias, void* workspace, size_t workspace_bytes,
+                    void* stream);
+int dd_linear_wgrad_n(const float* g_out, const float* x, int M, int cout, int cin, int products, float* g_weight, float* g_bias, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* The Adam update of every parameter tensor of a step in ONE launch behind a one-thread-per-tensor prologue (reference Trainer.py:150
  * `optimizer.step()` on torch.optim.Adam, Trainer.py:492-497).  `records` (device memory): one per parameter
  * tensor -- dense fp32 arrays of n elements each, `step` the tensor's step counter as torch keeps it for capturable optimizers (a
