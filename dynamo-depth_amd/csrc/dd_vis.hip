@@ -18,6 +18,8 @@
 
 #pragma STDC FP_CONTRACT OFF
 
+#include "dd_vis.h"      // after the pragma: the shared helpers are compiled unfused here as well
+
 namespace dd {
 
 constexpr int VIS_NT = 64;          // one wave per workgroup: the maximum is one shuffle tree and one atomic pair
@@ -49,17 +51,6 @@ __device__ __forceinline__ float vis_mod(float a, float b) {
   return r;
 }
 
-__device__ __forceinline__ unsigned vis_unit_byte(float x) { return (unsigned)(fminf(fmaxf(x, 0.f), 1.f) * 255.f); }
-
-// matplotlib's Normalize + Colormap.__call__ on fp32 data: the entry of the 256-entry table, -1 for NaN (black)
-__device__ __forceinline__ int vis_cmap_index(float x, float vmin, float vmax) {
-  const float s = ((x - vmin) / (vmax - vmin)) * 256.f;
-  if (s != s) return -1;
-  if (s < 0.f) return 0;
-  if (s >= 256.f) return 255;
-  return (int)s;
-}
-
 // four adjacent floats of a plane; lanes past the row's end read nothing
 __device__ __forceinline__ void vis_load4(const float* p, int valid, float (&v)[4]) {
   if (valid == 4 && ((uintptr_t)p & 15u) == 0u) {
@@ -68,30 +59,6 @@ __device__ __forceinline__ void vis_load4(const float* p, int valid, float (&v)[
   } else {
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = k < valid ? p[k] : 0.f;
-  }
-}
-
-__device__ __forceinline__ void vis_store4f(float* p, int valid, const float (&v)[4]) {
-  if (valid == 4 && ((uintptr_t)p & 15u) == 0u) {
-    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < valid) p[k] = v[k];
-  }
-}
-
-// four pixels r | g << 8 | b << 16 -> 12 bytes at dst
-__device__ __forceinline__ void vis_store4px(uint8_t* dst, int valid, const unsigned (&c)[4]) {
-  if (valid == 4 && ((uintptr_t)dst & 3u) == 0u) {
-    unsigned* d = reinterpret_cast<unsigned*>(dst);
-    d[0] = c[0] | (c[1] << 24);
-    d[1] = (c[1] >> 8) | (c[2] << 16);
-    d[2] = (c[2] >> 16) | (c[3] << 8);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < valid) dst[3 * k] = (uint8_t)(c[k] & 255u), dst[3 * k + 1] = (uint8_t)((c[k] >> 8) & 255u), dst[3 * k + 2] = (uint8_t)((c[k] >> 16) & 255u);
   }
 }
 

@@ -749,6 +749,27 @@ int dd_vis_frame(const float* color, const float* ref_color, const float* disp, 
 int dd_vis_flow_tiles(const float* side, const float* maxima, const int* tiles, int n_tiles, int R, int C, int H, int W, int n_frames,
                       float flow_mag_factor, int consistent_flow, uint8_t* panel, void* stream);
 
+/* Full-resolution depth export (predict.py; csrc/dd_export.hip): the depth metrics' definition of a prediction at a
+ * ground-truth pixel -- reference tools.py:42 F.interpolate(disp_scaled, gt size, mode="bilinear", align_corners=False) over
+ * tools.py:291-298 disp_to_depth, then 1 / x (tools.py:64) -- at EVERY pixel of the H x W source image, one pass over the output.
+ * disp (B,h,w) fp32: the network's sigmoid disparity.  disp_flipped NULL, or (B,h,w): the disparity of the horizontally mirrored
+ * image, NOT mirrored back; then l_mask [w] = 1 - clip(20 * (linspace(0,1,w) - 0.05), 0, 1) (host-made table, device memory) and
+ * every source tap (y,x) is first fused: l = disp[y,x], r = disp_flipped[y,w-1-x], m = 0.5*(l+r), lm = l_mask[x], rm = l_mask[w-1-x],
+ * d = (rm*l + lm*r) + ((1-lm) - rm)*m.  s = lo + span*d as dd_disp_to_depth; u = bilinear(s), d_up = bilinear(d), both fp32 in
+ * ATen's order (csrc/dd_bilinear.h) and without fused multiply-add: hipops/export.py export_depth_host is the same arithmetic.
+ * Outputs, each NULL or written at every element: depth (B,H,W) fp32 = 1/u; depth16 (B,H,W) = min(rint(depth * depth_scale), 65535)
+ * half to even, 0 for NaN and for a product below 0.5; rgb (B,H,W,3) = lut[entry of d_up] by matplotlib's Normalize(vmin, vmax) and
+ * 256-entry lookup as dd_vis_frame's disparity tile (lut: 256 words r | g << 8 | b << 16, device memory), black for NaN.
+ * dd_export_plane_u8: out (B,H,W) = (uint8)(clamp(bilinear(plane), 0, 1) * 255) of a (B,h,w) fp32 plane -- the motion mask at the
+ * source size (reference eval/visualize.py:113-114 shows it at the network's).
+ * hipErrorInvalidValue (1), nothing launched: disp / plane / out NULL, no output requested, l_mask without disp_flipped or the
+ * reverse, lut without rgb or the reverse, B, h, w, H or W below 1, H*W or h*w above 2^31-1, a non-positive depth bound, a float or
+ * table pointer that is not 4-byte aligned, a depth16 pointer that is not 2-byte aligned. */
+int dd_export_depth(const float* disp, const float* disp_flipped, const float* l_mask, int B, int h, int w, int H, int W, float min_depth,
+                    float max_depth, float depth_scale, const uint32_t* lut, float vmin, float vmax, float* depth, uint16_t* depth16, uint8_t* rgb,
+                    void* stream);
+int dd_export_plane_u8(const float* plane, int B, int h, int w, int H, int W, uint8_t* out, void* stream);
+
 const char* dd_error_string(int code);
 int dd_abi_version(void);
 
