@@ -23,6 +23,7 @@
 #pragma clang fp contract(off)
 
 #include "dd_bilinear.h"
+#include "dd_export_tap.h"
 #include "dd_math.h"
 #include "dd_vis.h"
 
@@ -42,17 +43,6 @@ struct ExportArgs {
   float sy, sx, depth_scale, vmin, vmax;
   DepthParams dp;
 };
-
-// the fused disparity of source tap (y, x) of one image
-template <bool FUSE>
-__device__ __forceinline__ float export_tap(const float* __restrict__ l_img, const float* __restrict__ r_img, const float* __restrict__ l_mask, int w, int y, int x) {
-  const float l = l_img[(size_t)y * w + x];
-  if (!FUSE) return l;
-  const float r = r_img[(size_t)y * w + (w - 1 - x)];
-  const float m = 0.5f * (l + r);
-  const float lm = l_mask[x], rm = l_mask[w - 1 - x];
-  return (rm * l + lm * r) + ((1.f - lm) - rm) * m;
-}
 
 __device__ __forceinline__ void export_store4h(uint16_t* p, int valid, const unsigned (&v)[4]) {
   if (valid == 4 && ((uintptr_t)p & 7u) == 0u) {

@@ -1,7 +1,8 @@
 """Depth for a folder of frames, at the frames' own resolution:
 
     python predict.py <frames dir> -l <checkpoint folder> [--depth_model ...] [--height H --width W] [-b B] [--out <dir>]
-                      [--save depth16 npy color] [--depth_scale 256] [--post_process] [--motion] [--intrinsics fx fy cx cy]
+                      [--save depth16 npy color cloud] [--depth_scale 256] [--post_process] [--motion] [--scene]
+                      [--intrinsics fx fy cx cy] [--cloud_stride 1] [--cloud_max_range R] [--cloud_edge 0.05] [--cloud_motion_thresh 0.5]
                       [--write_threads 8]
 
 The counterpart of the reference's quick demo on a few frames (its README's first offer; the demo notebook goes through
@@ -12,13 +13,21 @@ Per frame, named by the source file's stem:
     <out>/depth/<stem>.png        16-bit PNG (Pillow mode I;16): depth * depth_scale, rounded half to even, 65535 at and beyond the top
     <out>/depth_npy/<stem>.npy    float32 depth                                                                  (--save npy)
     <out>/color/<stem>.png        the disparity through matplotlib's plasma map                                  (--save color)
+    <out>/cloud/<stem>.ply        the frame as a coloured point cloud in its own camera coordinates (binary PLY)   (--save cloud)
     <out>/predict.json            min_depth, max_depth, depth_scale, the network resolution; depth is up to scale
 depth = 1 / bilinear(disp_to_depth(disp)) at the source size: the depth metrics' definition of a prediction (tools.py:42, 291-298),
 written by one kernel per batch (hipops.export, csrc/dd_export.hip); only the bytes that go to disk cross to the host.
 --post_process runs the network on the mirrored image too and fuses the two disparities (the literature's "PP").
 --motion reads the triplets (i-1, i, i+1) of the interior frames and also writes <out>/motion_mask/<stem>.png (the motion mask,
 bytes) and <out>/poses.txt: per interior frame its stem and the 16 numbers of the 4x4 transform from the frame to its predecessor.
+--save cloud back-projects the depth at every --cloud_stride-th pixel of the source frame (x right, y down, z forward; --intrinsics
+or KITTI's), drops what lies beyond --cloud_max_range and the "flying pixels" at depth edges (--cloud_edge, 0 turns it off), and
+writes the rest with the colours of the network-resolution frame: hipops.cloud, csrc/dd_cloud.hip, three launches per batch.
+--scene (with --motion, frames of one size) writes <out>/scene.ply: the points of every interior frame that the motion mask calls
+static (mask < --cloud_motion_thresh), moved by the chained poses into the coordinates of the first interior frame -- the static
+scene of the drive, the moving objects removed by the network's own mask.  Depth, and with it every cloud, is up to scale.
 """
+import contextlib
 import json
 import os
 import os.path as osp
@@ -34,11 +43,13 @@ from PIL import Image  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
 from datasets.folder_dataset import FolderDataset, sample_lines  # noqa: E402
+from hipops.cloud import chain_poses  # noqa: E402  (the scene's pose chain: numpy alone, tested without a GPU)
 from networks.layers import transformation_from_parameters  # noqa: E402
 from options import DynamoOptions  # noqa: E402
 from Trainer import Trainer  # noqa: E402
 
 MAX_THREADS = 16
+CLOUD = "cloud"         # --save cloud: not an output of export_depth
 SAVE = {"depth16": ("depth16", "depth", ".png"), "npy": ("depth", "depth_npy", ".npy"), "color": ("rgb", "color", ".png")}   # --save name -> (export output, folder, extension)
 SCALE_NOTE = "depth is up to scale: a self-supervised monocular network predicts it up to one unknown factor per model"
 
@@ -48,14 +59,23 @@ def parse(argv=None):
     p = options.p
     p.add_argument("frames_dir", type=str, help="a directory of .jpg / .jpeg / .png frames")
     p.add_argument("--out", type=str, default=None, help="output directory (default: <eval_dir>/predict/<frames dir's name>)")
-    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE), help="what to write per frame")
+    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE) + [CLOUD], help="what to write per frame")
     p.add_argument("--depth_scale", type=float, default=256.0, help="the 16-bit image holds depth * depth_scale")
     p.add_argument("--post_process", action="store_true", help="fuse the disparities of the image and of its mirror image")
     p.add_argument("--motion", action="store_true", help="triplets of frames: also the motion mask and the pose of every interior frame")
     p.add_argument("--write_threads", type=int, default=8, help="threads that encode and write the files (at most {})".format(MAX_THREADS))
     p.add_argument("--intrinsics", nargs=4, type=float, default=None, metavar=("fx", "fy", "cx", "cy"), help="in pixels of the frames (default: KITTI's)")
+    p.add_argument("--scene", action="store_true", help="with --motion: <out>/scene.ply, the static points of all interior frames in the first one's coordinates")
+    p.add_argument("--cloud_stride", type=int, default=1, help="clouds take every n-th pixel of the source frame in both directions")
+    p.add_argument("--cloud_max_range", type=float, default=None, help="clouds drop points beyond this depth (default: max_depth)")
+    p.add_argument("--cloud_edge", type=float, default=0.05, help="clouds drop pixels whose disparity taps differ by more than this fraction (0: keep them)")
+    p.add_argument("--cloud_motion_thresh", type=float, default=0.5, help="--scene keeps the pixels whose motion mask is below this")
     opt = options.parse(args=argv)
     opt.print_opt = False
+    if opt.scene and not opt.motion:
+        p.error("--scene needs --motion: the static scene is built from the motion masks and the poses of the interior frames")
+    if opt.cloud_stride < 1:
+        p.error("--cloud_stride is at least 1")
     if opt.load_ckpt == "" and opt.weights_init != "scratch":
         p.error("a checkpoint folder is needed: -l <folder> (--weights_init scratch runs untrained networks)")
     if opt.out is None:
@@ -88,9 +108,10 @@ def folder_dataset(opt, trainer, frames_dir, indices=None, intrinsics=None):
                          num_scales=len(opt.scales), is_train=False, path=True, intrinsics=intrinsics, **kwargs)
 
 
-def predict_batch(opt, trainer, inputs, post_process=False, motion=False):
+def predict_batch(opt, trainer, inputs, post_process=False, motion=False, cloud=False):
     """Uploads the batch and runs the networks: {"disp": (B,1,h,w)} on the device, with post_process "disp_flipped" (the disparity of the
-    mirrored image, not mirrored back), with motion "motion_mask" (B,1,h,w) and "cam_T_cam" (B,4,4) for frame 0 -> frame_ids[1]."""
+    mirrored image, not mirrored back), with motion "motion_mask" (B,1,h,w) and "cam_T_cam" (B,4,4) for frame 0 -> frame_ids[1], with
+    cloud "color" (B,3,h,w), the network-resolution frame."""
     with torch.no_grad():
         trainer.process_inputs(inputs)
         outputs = trainer.model(inputs)
@@ -103,6 +124,8 @@ def predict_batch(opt, trainer, inputs, post_process=False, motion=False):
             f = opt.frame_ids[1]
             res["motion_mask"] = outputs[("motion_mask", f, 0)]
             res["cam_T_cam"] = transformation_from_parameters(outputs[("axisangle", 0, f)], outputs[("translation", 0, f)], invert=True)
+        if cloud:
+            res["color"] = inputs[("color", 0, 0)]
     return res
 
 
@@ -110,12 +133,40 @@ def export_batch(opt, res, H, W, save=("depth16",), depth_scale=256.0):
     """The batch's files as device tensors, keyed by the output folder: one launch for the depth outputs, one for the motion mask."""
     from hipops.export import export_depth, export_plane_u8
     want = tuple(dict.fromkeys(SAVE[name][0] for name in save))
-    out = export_depth(res["disp"], H, W, disp_flipped=res.get("disp_flipped"), min_depth=opt.min_depth, max_depth=opt.max_depth,
-                       depth_scale=depth_scale, want=want)
-    files = {SAVE[name][1]: out[SAVE[name][0]] for name in save}
+    files = {}
+    if want:            # --save cloud alone asks for none of them
+        out = export_depth(res["disp"], H, W, disp_flipped=res.get("disp_flipped"), min_depth=opt.min_depth, max_depth=opt.max_depth,
+                           depth_scale=depth_scale, want=want)
+        files = {SAVE[name][1]: out[SAVE[name][0]] for name in save}
     if "motion_mask" in res:
         files["motion_mask"] = export_plane_u8(res["motion_mask"], H, W)
     return files
+
+
+def cloud_parameters(opt):
+    """The clouds' filters from the options: what predict.json records."""
+    max_range = getattr(opt, "cloud_max_range", None)
+    return {"stride": int(getattr(opt, "cloud_stride", 1)), "max_range": float(opt.max_depth if max_range is None else max_range),
+            "edge": float(getattr(opt, "cloud_edge", 0.05)), "motion_thresh": float(getattr(opt, "cloud_motion_thresh", 0.5))}
+
+
+def cloud_intrinsics(K, H, W):
+    """(fx, fy, cx, cy) in pixels of an H x W frame from the dataset's normalised intrinsics."""
+    return (float(K[0, 0]) * W, float(K[1, 1]) * H, float(K[0, 2]) * W, float(K[1, 2]) * H)
+
+
+def export_clouds(opt, res, H, W, intrinsics, params, pose=None, static=False):
+    """The batch's clouds as (records, offsets) on the device; `static`: the motion filter on (the scene), else never (a snapshot)."""
+    from hipops.cloud import export_cloud
+    return export_cloud(res["disp"], res["color"], H, W, intrinsics, disp_flipped=res.get("disp_flipped"), motion_mask=res["motion_mask"] if static else None,
+                        pose=pose, min_depth=opt.min_depth, max_depth=opt.max_depth, max_range=params["max_range"], edge=params["edge"],
+                        motion_thresh=params["motion_thresh"], stride=params["stride"])
+
+
+def _fetch_clouds(records, offsets):
+    """One small copy for the counts, then the used prefix of the records: (bytes of the batch's records, offsets on the host)."""
+    off = offsets.cpu().numpy()
+    return records[:int(off[-1])].cpu().numpy().reshape(-1), off
 
 
 def _write(path, array):
@@ -127,10 +178,16 @@ def _write(path, array):
 
 
 def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_scale=256.0, post_process=False, motion=False, intrinsics=None,
-                   write_threads=8):
+                   write_threads=8, scene=False, cloud=None):
     """Every frame of `frames_dir` (with motion: every interior frame) -> the files described above; returns the written paths.
-    The main thread launches and makes one copy to the host per batch and requested output; a thread pool encodes and writes."""
+    The main thread launches and makes one copy to the host per batch and requested output; a thread pool encodes and writes.
+    `cloud`: cloud_parameters(opt), for --save cloud and `scene`."""
+    from hipops.cloud import RECORD, ScenePly, write_ply
     save = tuple(dict.fromkeys(save))
+    want_cloud, save = CLOUD in save, tuple(name for name in save if name != CLOUD)
+    if scene and not motion:
+        raise ValueError("the scene cloud needs the motion networks (--motion)")
+    params = dict(cloud) if cloud is not None else cloud_parameters(opt)
     whole = folder_dataset(opt, trainer, frames_dir, None, intrinsics)
     n = len(whole.frames)
     indices = list(range(1, n - 1)) if motion else list(range(n))
@@ -139,21 +196,41 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
     by_size = {}            # frames of one source size share a batch: one export call serves it
     for i in indices:
         by_size.setdefault(whole.get_gt_dim(None, i, None), []).append(i)
-    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else [])
+    if scene and len(by_size) != 1:
+        raise ValueError("--scene needs frames of one size, {} holds {}".format(frames_dir, sorted(by_size)))
+    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else []) + ([CLOUD] if want_cloud else [])
     ext = {SAVE[name][1]: SAVE[name][2] for name in save}
     for folder in folders:
         os.makedirs(osp.join(out_dir, folder), exist_ok=True)
-    pending, poses = [], {}
-    with ThreadPoolExecutor(max_workers=min(max(int(write_threads), 1), MAX_THREADS)) as pool:
+    pending, poses, counts, scene_counts, used_intrinsics = [], {}, {}, {}, {}
+    scene_file, chain = (ScenePly(osp.join(out_dir, "scene.ply")) if scene else None), None
+    with ThreadPoolExecutor(max_workers=min(max(int(write_threads), 1), MAX_THREADS)) as pool, (scene_file or contextlib.nullcontext()):
         for (H, W), idx in sorted(by_size.items()):
             dataset = folder_dataset(opt, trainer, frames_dir, idx, intrinsics)
             loader = DataLoader(dataset, opt.batch_size, False, num_workers=opt.num_workers, pin_memory=trainer.device.type == "cuda", drop_last=False,
                                 collate_fn=dataset.collate, **trainer._worker_start())
             for inputs in loader:
                 stems = list(inputs["paths"])
-                res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion)
+                if want_cloud or scene:
+                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion, cloud=True)
+                    camera = used_intrinsics.setdefault("{}x{}".format(H, W), cloud_intrinsics(dataset.K, H, W))
+                else:
+                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion)
                 files = export_batch(opt, res, H, W, save, depth_scale)
+                clouds = export_clouds(opt, res, H, W, camera, params) if want_cloud else None
                 pose = res["cam_T_cam"].reshape(-1, 16).cpu().numpy() if motion else None
+                if scene:
+                    G = chain_poses(pose, chain)
+                    chain = G[-1]
+                    world = torch.from_numpy(np.ascontiguousarray(G[:, :3].astype(np.float32))).to(res["disp"].device)
+                    data, off = _fetch_clouds(*export_clouds(opt, res, H, W, camera, params, pose=world, static=True))
+                    scene_file.append(data)
+                    scene_counts.update({stem: int(off[b + 1] - off[b]) for b, stem in enumerate(stems)})
+                if clouds is not None:
+                    data, off = _fetch_clouds(*clouds)
+                    for b, stem in enumerate(stems):
+                        counts[stem] = int(off[b + 1] - off[b])
+                        pending.append(pool.submit(write_ply, osp.join(out_dir, CLOUD, stem + ".ply"), data[off[b] * RECORD:off[b + 1] * RECORD]))
                 for folder, tensor in files.items():
                     host = tensor.cpu().numpy()             # the batch's one copy of this output
                     for b, stem in enumerate(stems):
@@ -162,6 +239,8 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                     if motion:
                         poses[stem] = pose[b]
         written = [f.result() for f in pending]
+    if scene:
+        written.append(scene_file.close())
     if motion:
         path = osp.join(out_dir, "poses.txt")
         with open(path, "w") as fh:
@@ -170,9 +249,19 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                 fh.write(" ".join([stem] + ["{:.9g}".format(float(v)) for v in poses[stem]]) + "\n")
         written.append(path)
     path = osp.join(out_dir, "predict.json")
+    meta = {"min_depth": opt.min_depth, "max_depth": opt.max_depth, "depth_scale": depth_scale, "height": opt.height, "width": opt.width,
+            "depth_model": opt.depth_model, "post_process": bool(post_process), "frames": len(indices), "note": SCALE_NOTE}
+    if want_cloud or scene:
+        order = [whole.stem(i) for i in indices]
+        meta["cloud"] = dict(params, intrinsics={size: list(k) for size, k in used_intrinsics.items()}, note=SCALE_NOTE,
+                             convention="x right, y down, z forward; pixel centres at integer coordinates")
+        if want_cloud:
+            meta["cloud"]["points"] = {stem: counts[stem] for stem in order}
+        if scene:
+            meta["cloud"]["scene_points"] = {stem: scene_counts[stem] for stem in order}
+            meta["cloud"]["scene_total"] = int(sum(scene_counts.values()))
     with open(path, "w") as fh:
-        json.dump({"min_depth": opt.min_depth, "max_depth": opt.max_depth, "depth_scale": depth_scale, "height": opt.height, "width": opt.width,
-                   "depth_model": opt.depth_model, "post_process": bool(post_process), "frames": len(indices), "note": SCALE_NOTE}, fh, indent=2)
+        json.dump(meta, fh, indent=2)
     written.append(path)
     return written
 
@@ -181,7 +270,7 @@ def main(argv=None):
     opt = parse(argv)
     trainer = build_trainer(opt)
     written = predict_folder(opt, trainer, opt.frames_dir, opt.out, save=opt.save, depth_scale=opt.depth_scale, post_process=opt.post_process,
-                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads)
+                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads, scene=opt.scene, cloud=cloud_parameters(opt))
     print("{} files written to `{}`".format(len(written), opt.out))
     return written
 

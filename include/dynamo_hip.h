@@ -770,6 +770,33 @@ int dd_export_depth(const float* disp, const float* disp_flipped, const float* l
                     void* stream);
 int dd_export_plane_u8(const float* plane, int B, int h, int w, int H, int W, uint8_t* out, void* stream);
 
+/* Coloured point clouds (predict.py --save cloud / --scene; csrc/dd_cloud.hip): the depth dd_export_depth writes, at the
+ * candidate pixels (Y, X) of the H x W source image with Y % stride == 0 and X % stride == 0, back-projected through a pinhole camera
+ * (x right, y down, z forward, integer pixel coordinates as the reference's tools.BackprojectDepth), filtered, optionally moved by a
+ * rigid pose and compacted in order into 16-byte records: three little-endian floats x, y, z, then the bytes r, g, b, 255 -- the vertex
+ * layout of a binary PLY file.  fp32, unfused; hipops/cloud.py export_cloud_host is the definition in numpy, bit for bit.
+ * disp, disp_flipped, l_mask as dd_export_depth.  color (B,3,h,w) in [0,1]: the network-resolution frame; a record's colour is
+ * vis_unit_byte of its bilinear sample.  motion_mask NULL or (B,h,w).  pose NULL or (B,3,4) row-major [R | t] per frame.
+ * fx, fy, cx, cy: in pixels of the H x W frame; 1/fx and 1/fy are evaluated in double and rounded to fp32 once.
+ * Kept: depth > 0 && depth <= max_range; with edge > 0 also (smax - smin) <= edge * smin over the four scaled disparity taps; with a
+ * motion mask also bilinear(mask) < motion_thresh.  Every comparison is false for NaN.
+ *   point = (((float)X - cx) / fx * depth, ((float)Y - cy) / fy * depth, depth), with a pose p'_k = ((R[k,0] x + R[k,1] y) + R[k,2] z) + t[k].
+ * records: room for every candidate, B * ceil(H/stride) * ceil(W/stride) * 16 bytes, 16-byte aligned; the kept candidates of frame 0 in
+ *   row-major (Y, X) order, then frame 1, ...; bytes past offsets[B] * 16 are not touched.
+ * offsets (B+1) int64: the records of frame b are offsets[b] .. offsets[b+1] - 1.
+ * workspace: dd_export_cloud_workspace_bytes(B, H, W, stride), 8-byte aligned; every word the call reads it has written before.
+ * Three launches (count, scan, write), integer placement, no atomics: every output byte is the same from run to run.
+ * hipErrorInvalidValue (1), nothing launched: disp, color, records, offsets or workspace NULL, l_mask without disp_flipped or the
+ * reverse, B, h, w, H, W or stride below 1, H*W or h*w above 2^31-1, more than 2^32 - 1 lanes (B * ceil(H/stride) *
+ * ceil(ceil(W/stride) / 256) * 256), fx or fy zero or not finite, a non-positive depth bound, a float pointer that is not 4-byte
+ * aligned, records not 16-byte, offsets or workspace not 8-byte aligned, a workspace that is too small (the query returns 0 for sizes
+ * that are refused). */
+size_t dd_export_cloud_workspace_bytes(int B, int H, int W, int stride);
+int dd_export_cloud(const float* disp, const float* disp_flipped, const float* l_mask, const float* color, const float* motion_mask,
+                    const float* pose, int B, int h, int w, int H, int W, float fx, float fy, float cx, float cy, float min_depth,
+                    float max_depth, float max_range, float edge, float motion_thresh, int stride, void* records, long long* offsets,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 const char* dd_error_string(int code);
 int dd_abi_version(void);
 
