@@ -412,6 +412,221 @@ static int launch_fused(const float* x, const void* pack1, const void* pack2, co
   return (int)hipGetLastError();
 }
 
+// ---- the same block at C = 224 (LiteMono's stage 3: 5 760 / 11 520 rows, hidden 1344 = 42 blocks) -----------------------------------
+// mlp_fwd_kernel's arithmetic and operand layouts; what differs is what C = 224 does not fit:
+//   * registers: 14 x 3 x fragments (168) + 7 output accumulators (112) want more than half the file, so ONE wave per SIMD
+//     (__launch_bounds__(256, 1): 2 x 256 registers per lane, and what a VALU instruction touches must sit in the first 256) and NO
+//     weight prefetch in registers (with one, even of 11 fragments per wave, the kernel spilled): the fragments go global -> LDS
+//     directly, W1's and W2's halves of the LDS buffer refilled in turn, each while the other one is being read;
+//   * parallelism: 128 rows per workgroup are 90 workgroups at 11 520 rows, so blockIdx.y takes one of S contiguous ranges of hidden
+//     blocks ([s * 42 / S, (s + 1) * 42 / S): uneven when S does not divide 42, never empty for S <= 42) and stores ONE partial
+//     [S][M][224]; mlp_fold224_kernel adds the partials in split order behind b2.  S = 1 stores the result itself.  No atomics, no
+//     zero-fill, bit-reproducible for a given S;
+//   * one wave per SIMD has nobody to hide its GELU behind, so the loop is skewed by one block: the first GEMM of block hb + 1 is issued
+//     beside the bias + GELU + split of block hb (independent instructions in one scheduling region), then the second GEMM of block hb.
+constexpr int C3 = 224, KS3 = C3 / 16, NB3 = C3 / 32, NHB3 = 6 * C3 / 32;
+constexpr int NF3 = KS3 * 3;                                    // fragments per hidden block and operand: 14 x 3 = 7 x 2 x 3 = 42
+constexpr int BR3 = (NF3 + 3) / 4;
+constexpr int MLP3_LDS = 2 * NF3 * FRAG + 6 * C3 * 4;           // W1 block | W2 block | b1
+static_assert(NF3 == NB3 * 6, "both operands of a hidden block have the same number of fragments");
+
+template <int NP>
+__global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restrict__ x, const uint4* __restrict__ pack1, const uint4* __restrict__ pack2,
+                                                            const float* __restrict__ b1, const float* __restrict__ bias, int M, int S,
+                                                            float* __restrict__ dst) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  unsigned char* const s_w1 = smem;
+  unsigned char* const s_w2 = smem + NF3 * FRAG;
+  float* const s_b1 = reinterpret_cast<float*>(smem + 2 * NF3 * FRAG);
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 3, hh = lane >> 5;
+  const int row0 = (int)blockIdx.x * 128 + wave * 32;
+  const int split = (int)blockIdx.y, hb0 = split * NHB3 / S, hb1 = (split + 1) * NHB3 / S;
+
+  for (int i = tid; i < 6 * C3; i += 256) s_b1[i] = b1[i];
+  uint4 xf[KS3][3];
+  {
+    const float* xp = x + (size_t)min(row0 + (lane & 31), M - 1) * C3 + hh * 8;
+#pragma unroll
+    for (int ks = 0; ks < KS3; ++ks) {
+      const float4 v0 = *reinterpret_cast<const float4*>(xp + ks * 16), v1 = *reinterpret_cast<const float4*>(xp + ks * 16 + 4);
+      unsigned p[3][4];
+      split2(v0.x, v0.y, p[0][0], p[1][0], p[2][0]);
+      split2(v0.z, v0.w, p[0][1], p[1][1], p[2][1]);
+      split2(v1.x, v1.y, p[0][2], p[1][2], p[2][2]);
+      split2(v1.z, v1.w, p[0][3], p[1][3], p[2][3]);
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) xf[ks][pc] = make_uint4(p[pc][0], p[pc][1], p[pc][2], p[pc][3]);
+    }
+  }
+  // One operand's fragments of hidden block hb (both packs: 42 fragments per block) go global -> LDS without passing registers
+  // (global_load_lds_dwordx4: 1 KB per wave-instruction, lane l at byte 16 l, which is the fragment's own order); wave w moves the
+  // fragments w, w + 4, ...  The compiler does not count these loads: wait_barrier() waits for them, and nothing reads a buffer
+  // between its dma() and the next wait_barrier().
+  const unsigned lds0 = (unsigned)reinterpret_cast<size_t>(smem);
+  auto dma = [&](const uint4* pack, int hb, unsigned char* s_w) {
+    const uint4* src = pack + (size_t)hb * (NF3 * 64) + lane;
+#pragma unroll
+    for (int r = 0; r < BR3; ++r) {
+      const int f = min(wave + 4 * r, NF3 - 1);     // 42 = 4 x 10 + 2: in the last round waves 2 and 3 repeat wave 1's (the same bytes; no branch)
+      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(s_w - smem) + f * FRAG);
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(src + f * 64), "s"(dst) : "memory");
+    }
+  };
+  // every load and LDS operation of this wave has completed (the weight fragments it moved have landed), then the barrier
+  auto wait_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+
+  // One scheduling region per MFMA step (six products on one pair of fragments): the step's MFMAs, the LDS reads of the NEXT step's
+  // weight fragments, and one slice of the activation's VALU work.  (Left to itself the scheduler hoists the fragment reads of a whole
+  // unrolled GEMM and spills.)
+  f16v acc2[NB3];
+#pragma unroll
+  for (int n = 0; n < NB3; ++n)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc2[n][r] = 0.f;
+  auto read_w = [&](const unsigned char* s_w, int f, uint4 (&wf)[3]) {
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) wf[pc] = *reinterpret_cast<const uint4*>(s_w + lane * 16 + (f * 3 + pc) * FRAG);
+  };
+  // bias + GELU on the first GEMM's accumulator (register r: hidden unit hb * 32 + (r & 3) + 8 (r >> 2) + 4 hh of pixel lane & 31) and
+  // the split into the second GEMM's A fragments (registers 8 j .. 8 j + 7 are step j), in 21 slices: 0..10 and 14..18 one GELU each,
+  // 11, 12 the fragments of step 0, 19, 20 those of step 1 -- fourteen slices beside the first GEMM of the next block, seven beside
+  // step 0 of the second GEMM
+  float hv[16];
+  uint4 hf[2][3];
+  auto slice = [&](const f16v& acc, int hb, int i) {
+    const int r = i < 11 ? i : i - 3;
+    if (i < 11 || (i >= 14 && i < 19)) {
+      hv[r] = gelu_erf(acc[r] + s_b1[hb * 32 + 8 * (r >> 2) + 4 * hh + (r & 3)]);
+      asm volatile("" : "+v"(hv[r]));              // computed HERE, beside this step's MFMAs (else it sinks to its first use)
+    }
+    if (i == 11 || i == 12 || i == 19 || i == 20) {
+      const int j = i >= 19, q0 = (i == 12 || i == 20) ? 2 : 0;
+      unsigned p[3][2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        split2(hv[8 * j + 2 * (q0 + q)], hv[8 * j + 2 * (q0 + q) + 1], p[0][q], p[1][q], p[2][q]);
+        asm volatile("" : "+v"(p[0][q]), "+v"(p[1][q]), "+v"(p[2][q]));
+      }
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) {
+        if (q0 == 0) { hf[j][pc].x = p[pc][0]; hf[j][pc].y = p[pc][1]; }
+        else { hf[j][pc].z = p[pc][0]; hf[j][pc].w = p[pc][1]; }
+      }
+    }
+  };
+  // first GEMM, transposed: h^T (32 hidden x 32 pixels) = W1 block . x^T, with slices 0..13 of block hb's activation when `act`
+  auto gemm1 = [&](f16v& acc, const f16v& prev, int hb, auto act) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    uint4 wf[2][3];
+    read_w(s_w1, 0, wf[0]);
+#pragma unroll
+    for (int ks = 0; ks < KS3; ++ks) {
+      if (ks + 1 < KS3) read_w(s_w1, ks + 1, wf[(ks + 1) & 1]);
+#pragma unroll
+      for (int t = 6 - NP; t < 6; ++t)
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, wf[ks & 1][cm::kPieceA[t]]), __builtin_bit_cast(bf8, xf[ks][cm::kPieceB[t]]), acc, 0, 0, 0);
+      if (decltype(act)::value) slice(prev, hb, ks);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // second GEMM: out (32 pixels x 224) += h (A operand, straight from the registers) . W2 block, with slices 14..20 beside step 0
+  auto gemm2 = [&](const f16v& prev, int hb) {
+    uint4 wf[2][3];
+    read_w(s_w2, 0, wf[0]);
+#pragma unroll
+    for (int i = 0; i < 2 * NB3; ++i) {
+      const int j = i / NB3, n = i - j * NB3;
+      if (i + 1 < 2 * NB3) read_w(s_w2, ((i + 1) % NB3) * 2 + (i + 1) / NB3, wf[(i + 1) & 1]);
+#pragma unroll
+      for (int t = 6 - NP; t < 6; ++t)
+        acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, hf[j][cm::kPieceA[t]]), __builtin_bit_cast(bf8, wf[i & 1][cm::kPieceB[t]]), acc2[n], 0, 0, 0);
+      if (j == 0) slice(prev, hb, 14 + n);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  float bv[NB3];         // what the store adds (b2, or nothing to a partial), fetched first (dd_store_tile.h)
+#pragma unroll
+  for (int n = 0; n < NB3; ++n) bv[n] = tile_bias(bias, n * 32 + (lane & 31), C3, pack2);
+
+  // prologue: W1 of the first block, its first GEMM, then W1 of the second block in place and W2 of the first one on its way
+  f16v acc1;
+  dma(pack1, hb0, s_w1);
+  wait_barrier();                                  // (b1 is in place too)
+  gemm1(acc1, acc1, hb0, std::false_type{});
+  wait_barrier();                                  // every wave has read W1 of the first block
+  dma(pack1, min(hb0 + 1, hb1 - 1), s_w1);
+  wait_barrier();
+  dma(pack2, hb0, s_w2);
+  // here, for every hb: acc1 = the pre-activation of block hb less its bias, s_w1 = W1 of block hb + 1, W2 of block hb on its way to s_w2
+  auto block = [&](int hb, auto more) {
+    f16v accn;
+    if (decltype(more)::value) gemm1(accn, acc1, hb, std::true_type{});        // block hb + 1, beside the VALU work of block hb
+    else {
+#pragma unroll
+      for (int i = 0; i < KS3; ++i) slice(acc1, hb, i);
+    }
+    wait_barrier();                                // W2 of block hb is in place, every wave has read s_w1
+    if (decltype(more)::value) dma(pack1, min(hb + 2, hb1 - 1), s_w1);
+    gemm2(acc1, hb);
+    if (decltype(more)::value) {
+      wait_barrier();                              // W1 of block hb + 2 is in place, every wave has read s_w2
+      dma(pack2, hb + 1, s_w2);
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc1[r] = accn[r];
+    }
+  };
+  for (int hb = hb0; hb < hb1 - 1; ++hb) block(hb, std::true_type{});
+  block(hb1 - 1, std::false_type{});
+
+  float* const out = dst + (size_t)split * M * C3;
+  auto tail = [&](auto full) {
+    const int row = row0 + 4 * hh;
+#pragma unroll
+    for (int n = 0; n < NB3; ++n)
+      store_acc32<decltype(full)::value>(acc2[n], bv[n], out + (size_t)row * C3 + n * 32 + (lane & 31), (size_t)C3, M - row, StoreF32{});
+  };
+  if ((int)blockIdx.x * 128 + 128 <= M) tail(std::true_type{});
+  else tail(std::false_type{});
+}
+
+// y = b2 + partial 0 + partial 1 + ... in that order, four channels per thread (224 = 56 quads per row)
+__global__ __launch_bounds__(256) void mlp_fold224_kernel(const float4* __restrict__ partial, const float4* __restrict__ b2, int S, size_t quads, float4* __restrict__ y) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= quads) return;
+  float4 a = b2[i % (C3 / 4)];
+  for (int s = 0; s < S; ++s) {
+    const float4 p = partial[(size_t)s * quads + i];
+    a.x += p.x; a.y += p.y; a.z += p.z; a.w += p.w;
+  }
+  y[i] = a;
+}
+
+// S from the row count: 128 rows per workgroup, one workgroup per CU (LDS and registers), and not more workgroups than the 256 CUs:
+// a second round doubles the time (the 528-on-512 note of dd_linear_wgrad.hip)
+static int mlp224_splits(int M) {
+  const int groups = (M + 127) / 128, n = 256 / groups;
+  return n < 1 ? 1 : n > NHB3 ? NHB3 : n;
+}
+
+template <int NP>
+static int launch_fused224(const float* x, const void* pack1, const void* pack2, const float* b1, const float* b2, int M, int S, float* y, float* partial,
+                           hipStream_t stream) {
+  auto kern = mlp_fwd224_kernel<NP>;
+  static dd::LdsAttrOnce lds_attr;          // per instantiation and device (dd_attr.h)
+  if (const int rc = lds_attr.ensure(reinterpret_cast<const void*>(kern), MLP3_LDS)) return rc;
+  hipLaunchKernelGGL(kern, dim3((M + 127) / 128, S), dim3(256), MLP3_LDS, stream, x, static_cast<const uint4*>(pack1), static_cast<const uint4*>(pack2), b1,
+                     S == 1 ? b2 : nullptr, M, S, S == 1 ? y : partial);
+  if (S == 1) return (int)hipGetLastError();
+  const size_t quads = (size_t)M * (C3 / 4);
+  hipLaunchKernelGGL(mlp_fold224_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(partial),
+                     reinterpret_cast<const float4*>(b2), S, quads, reinterpret_cast<float4*>(y));
+  return (int)hipGetLastError();
+}
+
 // backward of the activation between the two Linears, one pass: post = GELU(pre) (the second Linear's weight gradient wants the
 // activated tensor, which the forward never wrote) and g <- g * GELU'(pre) in place (cdf + x pdf, ATen's GeluBackwardCUDAKernelImpl formula on erf_poly)
 __global__ __launch_bounds__(256) void gelu_pair_kernel(const float4* __restrict__ pre, float4* __restrict__ g, float4* __restrict__ post, size_t quads) {
@@ -463,7 +678,33 @@ extern "C" int dd_mlp_pack(const float* w1, long long s1_n, long long s1_k, cons
   return (int)hipGetLastError();
 }
 
-extern "C" int dd_mlp_fwd_supported(int C) { return (C == 64 || C == 128) ? 1 : 0; }
+extern "C" int dd_mlp_fwd_supported(int C) { return (C == 64 || C == 128 || C == 224) ? 1 : 0; }
+
+extern "C" int dd_mlp_fwd_splits(int M, int C) { return (C == dd::pw::C3 && M >= 1) ? dd::pw::mlp224_splits(M) : 1; }
+
+extern "C" size_t dd_mlp_fwd_workspace_bytes(int M, int C, int splits) {
+  if (M < 1 || !dd_mlp_fwd_supported(C) || splits < 0 || splits > dd::pw::NHB3) return 0;
+  const int S = splits ? splits : dd_mlp_fwd_splits(M, C);
+  return (C == dd::pw::C3 && S > 1) ? (size_t)S * M * C * sizeof(float) : 0;
+}
+
+extern "C" int dd_mlp_fwd_n(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, int products,
+                            int splits, float* y, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace dd::pw;
+  if (C != C3) return (products == 6 && splits <= 1) ? dd_mlp_fwd(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, C, y, stream) : (int)hipErrorInvalidValue;
+  if (!x || !pack_fwd1 || !pack_fwd2_fused || !b1 || !b2 || !y || M < 1 || splits < 0 || splits > NHB3) return (int)hipErrorInvalidValue;
+  if (products != 6 && products != 3 && products != 1) return (int)hipErrorInvalidValue;
+  if ((reinterpret_cast<unsigned long long>(x) | reinterpret_cast<unsigned long long>(y) | reinterpret_cast<unsigned long long>(b2) |
+       reinterpret_cast<unsigned long long>(workspace)) & 15ull)
+    return (int)hipErrorInvalidValue;
+  const int S = splits ? splits : mlp224_splits(M);
+  if (S > 1 && (!workspace || workspace_bytes < dd_mlp_fwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  return products == 6 ? launch_fused224<6>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
+       : products == 3 ? launch_fused224<3>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
+                       : launch_fused224<1>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s);
+}
 
 extern "C" int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, float* y, void* stream) {
   if (!x || !pack_fwd1 || !pack_fwd2_fused || !b1 || !b2 || !y || M < 1 || (reinterpret_cast<unsigned long long>(x) & 15ull)) return (int)hipErrorInvalidValue;
@@ -471,6 +712,7 @@ extern "C" int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pac
   switch (C) {
     case 64: return dd::pw::launch_fused<64>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
     case 128: return dd::pw::launch_fused<128>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
+    case 224: return dd::pw::launch_fused224<6>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, 1, y, nullptr, s);      // unsplit: dd_mlp_fwd_n fills the chip
     default: return (int)hipErrorInvalidValue;
   }
 }

@@ -241,6 +241,9 @@ def declare(lib):
         "dd_mlp_pack": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v, v]),
         "dd_mlp_fwd_supported": (i, [i]),
         "dd_mlp_fwd": (i, [v, v, v, v, v, i, i, v, v]),
+        "dd_mlp_fwd_splits": (i, [i, i]),
+        "dd_mlp_fwd_workspace_bytes": (z, [i, i, i]),
+        "dd_mlp_fwd_n": (i, [v, v, v, v, v, i, i, i, i, v, v, z, v]),
         "dd_pw_gemm": (i, [v, v, v, i, i, i, i, v, v]),
         "dd_gelu_pair": (i, [v, v, v, z, v]),
         "dd_linear_wgrad_supported": (i, [i, i, i]),
@@ -284,7 +287,7 @@ EXPORTED = (
     "dd_conv3x3_mfma_wgrad_workspace_bytes", "dd_conv3x3_mfma_bwd_weight", "dd_conv3x3_mfma_bwd_weight_n",
     "dd_conv3x3_half_supported", "dd_conv3x3_half_pack_bytes", "dd_conv3x3_half_pack", "dd_conv3x3_half",
     "dd_conv3x3_half_wgrad_workspace_bytes", "dd_conv3x3_half_bwd_weight",
-    "dd_pw_gemm_pack_bytes", "dd_mlp_pack", "dd_pw_gemm", "dd_gelu_pair", "dd_mlp_fwd_supported", "dd_mlp_fwd",
+    "dd_pw_gemm_pack_bytes", "dd_mlp_pack", "dd_pw_gemm", "dd_gelu_pair", "dd_mlp_fwd_supported", "dd_mlp_fwd", "dd_mlp_fwd_splits", "dd_mlp_fwd_workspace_bytes", "dd_mlp_fwd_n",
     "dd_linear_wgrad_supported", "dd_linear_wgrad_workspace_bytes", "dd_linear_wgrad", "dd_linear_wgrad_n",
     "dd_error_string", "dd_abi_version",
 )

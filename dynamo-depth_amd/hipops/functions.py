@@ -1045,20 +1045,29 @@ def mlp_fused_calls():
     return _MLP_FUSED_CALLS[0]
 
 
+# rows below which dd_mlp_fwd leaves the block to the library, by width: C = 64 / 128 need enough 128-row workgroups to fill the chip;
+# C = 224 splits the hidden range over workgroups instead (dd_mlp_fwd_n) and is ahead from the crossover measured in profiles/mlp_stage3.txt
+_MLP_FUSED_MIN_ROWS = {64: 16384, 128: 16384, 224: 3840}
+
+
 def _mlp_block_ok(y, block):
-    """dd_mlp_fwd covers this block: fp32, contiguous (B,H,W,C) with enough rows to fill the chip, 6x expansion, erf GELU, C = 64 or 128."""
+    """dd_mlp_fwd covers this block: fp32, contiguous (B,H,W,C) with enough rows for its width (_MLP_FUSED_MIN_ROWS; DD_MLP_FUSED_MIN_ROWS
+    overrides it for every width), 6x expansion, erf GELU, C = 64, 128 or 224."""
     l1, l2 = block.pwconv1, block.pwconv2
     if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and l1.weight.dtype == torch.float32):
         return False
-    if y.shape[0] * y.shape[1] * y.shape[2] < int(os.environ.get("DD_MLP_FUSED_MIN_ROWS", "16384")):
+    min_rows = os.environ.get("DD_MLP_FUSED_MIN_ROWS")
+    if y.shape[0] * y.shape[1] * y.shape[2] < (int(min_rows) if min_rows is not None else _MLP_FUSED_MIN_ROWS.get(l1.in_features, 16384)):
         return False
     return bool(l1.bias is not None and l2.bias is not None and l1.out_features == 6 * l1.in_features and l2.in_features == l1.out_features
                 and l2.out_features == l1.in_features and y.shape[-1] == l1.in_features and isinstance(block.act, torch.nn.GELU)
                 and getattr(block.act, "approximate", "none") == "none" and L.load().dd_mlp_fwd_supported(l1.in_features))
 
 
-def _mlp_fwd_launch(y, w1, b1, w2, b2):
-    """pwconv2(GELU(pwconv1(y))) in one kernel: pack both weights (one launch), then dd_mlp_fwd; the hidden tensor never exists."""
+def _mlp_fwd_launch(y, w1, b1, w2, b2, splits=0):
+    """pwconv2(GELU(pwconv1(y))) in one kernel: pack both weights (one launch), then dd_mlp_fwd; the hidden tensor never exists.
+    C = 224 (stage 3) goes through dd_mlp_fwd_n: mfma_products() honoured, the hidden range split over `splits` workgroups per row group
+    (0: the library chooses from the row count) and the partials folded by a second launch."""
     lib = L.load()
     B, H, W, Cc = y.shape
     hid, M = w1.shape[0], B * H * W
@@ -1067,13 +1076,18 @@ def _mlp_fwd_launch(y, w1, b1, w2, b2):
     p0, stream = packs.data_ptr(), L.current_stream()
     L.check(lib.dd_mlp_pack(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, None, None, None, p0 + nb1, stream), "dd_mlp_pack")
     out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
+    if Cc == 224:
+        nbytes = _ws_bytes("dd_mlp_fwd_workspace_bytes", M, Cc, splits)
+        ws = _ws(nbytes, y.device)
+        L.check(lib.dd_mlp_fwd_n(_p(y), p0, p0 + nb1, _p(b1), _p(b2), M, Cc, mfma_products(), splits, _p(out), _p(ws), nbytes, stream), "dd_mlp_fwd_n")
+        return out
     L.check(lib.dd_mlp_fwd(_p(y), p0, p0 + nb1, _p(b1), _p(b2), M, Cc, _p(out), stream), "dd_mlp_fwd")
     return out
 
 
 def mlp_fused_ok(y, block):
     """dd_mlp_fwd covers this block's pwconv2(GELU(pwconv1(y))) in ONE kernel: a pass that keeps nothing for a backward (the
-    statistics-only side batch, evaluation), fp32, C = 64 or 128, erf GELU, enough rows to fill the chip."""
+    statistics-only side batch, evaluation), fp32, C = 64, 128 or 224, erf GELU, enough rows for that width (_mlp_block_ok)."""
     if torch.is_grad_enabled() or os.environ.get("DD_STOCK_MLP_FUSED", "0") == "1" or torch.is_autocast_enabled():
         return False
     return _mlp_block_ok(y, block)

@@ -668,10 +668,16 @@ int dd_conv3x3_half_bwd_weight(const void* x, const void* g_out, int B, int Hi, 
  * dd_mlp_pack: ONE launch packs up to four operands of a block from w1 (hidden,C) and w2 (C,hidden), each addressed through its two
  * element strides: pack_fwd1 (N = hidden, K = C), pack_fwd2 (N = C, K = hidden), and for the data gradients pack_bwd2 = w2 transposed
  * (g_post = g . w2: N = hidden, K = C) and pack_bwd1 = w1 transposed (g_y = g_pre . w1: N = C, K = hidden); NULL skips an operand.
- * dd_mlp_fwd (C = 64 or 128: dd_mlp_fwd_supported): the whole block forward out (M,C) = GELU(x . w1^T + b1) . w2^T + b2 in ONE kernel for
+ * dd_mlp_fwd (C = 64, 128 or 224: dd_mlp_fwd_supported): the whole block forward out (M,C) = GELU(x . w1^T + b1) . w2^T + b2 in ONE kernel for
  * passes that keep nothing for a backward (the statistics-only side batch of Trainer.py:215-222's three-frame depth pass, evaluation):
  * the 6C-wide hidden tile stays in accumulator registers between the two GEMMs; operands pack_fwd1 and pack_fwd2_fused
  * (dd_pw_gemm_pack_bytes(C, hidden) bytes: w2 by hidden block, contraction order = the accumulator's register order).
+ * dd_mlp_fwd_n: the same with `products` (6 / 3 / 1 as dd_conv3x3_mfma_n) and, at C = 224 -- stage 3's few rows: 128 per workgroup would
+ * leave most of the chip idle -- the 42 hidden blocks split over `splits` workgroups per row group (0: dd_mlp_fwd_splits(M, C), chosen so
+ * that the grid is one round of the chip; 1..42 forces it): each writes one partial (splits, M, 224) into `workspace`
+ * (dd_mlp_fwd_workspace_bytes(M, C, splits) bytes, 16-byte aligned, private to the call's stream; nothing for splits = 1) and a second
+ * launch adds them in split order behind b2 (16-byte aligned) -- no atomics, no zero-fill, bit-reproducible for a given split count.
+ * C = 64 / 128 take products = 6 and splits <= 1 only (dd_mlp_fwd itself).
  * dd_gelu_pair: the activation's backward in one pass over n elements (n % 4 == 0, 16-byte aligned): post = GELU(pre) (what the second
  * Linear's weight gradient contracts with) and g_inout <- g_inout * GELU'(pre), ATen's arithmetic.  Everything is bit-reproducible. */
 size_t dd_pw_gemm_pack_bytes(int N, int K);
@@ -679,6 +685,10 @@ int dd_mlp_pack(const float* w1, long long s1_n, long long s1_k, const float* w2
                 void* pack_fwd2, void* pack_bwd2, void* pack_bwd1, void* pack_fwd2_fused, void* stream);
 int dd_mlp_fwd_supported(int C);
 int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, float* y, void* stream);
+int dd_mlp_fwd_splits(int M, int C);
+size_t dd_mlp_fwd_workspace_bytes(int M, int C, int splits);
+int dd_mlp_fwd_n(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, int products, int splits,
+                 float* y, void* workspace, size_t workspace_bytes, void* stream);
 int dd_pw_gemm(const float* x, const void* pack, const float* bias, int M, int K, int N, int gelu_in, float* y, void* stream);
 int dd_gelu_pair(const float* pre, float* g_inout, float* post, size_t n, void* stream);
 
