@@ -4,7 +4,12 @@
 // Stock PyTorch-ROCm runs 3 MIOpen kernels per BN forward, 3 per backward, plus one element-wise kernel per activation /
 // residual in each direction: ~570 + ~250 launches per training step, almost all at the ~5 us launch floor.  Here a BN(+act
 // +residual) is 2 launches forward and 2 backward; every pass is a coalesced float4 stream over [rows, C].
-// Sums: fp32 inside a chunk of rows, fp64 across lanes and chunks, fixed order -> run-to-run reproducible.
+// Forward statistics: every thread adds x and x * x of its rows in fp64 (the fp32 loads widen exactly), the lanes of a chunk and the
+// chunks are added in fp64 in a fixed order and no total is rounded to fp32 on the way, so var = E[x^2] - mean^2 is formed from sums
+// that are good to ~2^-53 * (additions on the path): the cancellation at mean^2 costs (mean / sigma)^2 * 1e-14 of the variance, not
+// (mean / sigma)^2 * 2^-24.  The pass stays bound by its loads (twelve fp64 operations per 16 bytes read).  Backward sums (of g' and
+// g' * xhat, which do not cancel): fp32 per thread, fp64 across lanes and chunks, each total rounded to fp32.  Fixed order
+// everywhere -> run-to-run reproducible.
 #include <hip/hip_runtime.h>
 
 #include "../../include/dynamo_hip.h"
@@ -35,36 +40,76 @@ static inline BnGeom bn_geom(int C) {
   return g;
 }
 
-// ---- pass 1 (forward): per-chunk sum and sum of squares per channel ----------------------------------------------------
-// partial[chunk][2][C].  thread = (row lane, 4 channels)
+// ---- pass 1 (forward): per-chunk sum and sum of squares per channel, fp64 throughout -----------------------------------
+// partial[chunk][2][C] doubles.  thread = (row lane, 4 channels)
 template <typename T>
 __global__ __launch_bounds__(BN_NT) void bn_stats_kernel(const T* __restrict__ x, long long rows, int C, int lanes, int rows_per_chunk,
-                                                          float* __restrict__ partial) {
-  extern __shared__ float red[];                             // [lanes][2][C]
+                                                          double* __restrict__ partial) {
+  extern __shared__ double red64[];                          // [lanes][2][C]
   const int C4 = C >> 2;
   const int lane = threadIdx.x / C4, c4 = threadIdx.x - lane * C4;
   const long long r0 = (long long)blockIdx.x * rows_per_chunk;
   long long r1 = r0 + rows_per_chunk;
   if (r1 > rows) r1 = rows;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 4
   for (long long r = r0 + lane; r < r1; r += lanes) {
     const float4 v = IO<T>::load4(x, r * C4 + c4);
-    s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-    s2.x = fmaf(v.x, v.x, s2.x); s2.y = fmaf(v.y, v.y, s2.y); s2.z = fmaf(v.z, v.z, s2.z); s2.w = fmaf(v.w, v.w, s2.w);
+    const double a = (double)v.x, b = (double)v.y, c = (double)v.z, d = (double)v.w;
+    s1[0] += a; s1[1] += b; s1[2] += c; s1[3] += d;
+    s2[0] = fma(a, a, s2[0]); s2[1] = fma(b, b, s2[1]); s2[2] = fma(c, c, s2[2]); s2[3] = fma(d, d, s2[3]);
   }
-  reinterpret_cast<float4*>(red)[(lane * 2 + 0) * C4 + c4] = s1;
-  reinterpret_cast<float4*>(red)[(lane * 2 + 1) * C4 + c4] = s2;
+  double* mine = red64 + (size_t)lane * 2 * C + c4 * 4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    mine[j] = s1[j];
+    mine[C + j] = s2[j];
+  }
   __syncthreads();
-  float* dst = partial + (size_t)blockIdx.x * 2 * C;
+  double* dst = partial + (size_t)blockIdx.x * 2 * C;
   for (int i = threadIdx.x; i < 2 * C; i += blockDim.x) {
     double s = 0.0;
-    for (int l = 0; l < lanes; ++l) s += (double)red[l * 2 * C + i];
-    dst[i] = (float)s;
+    for (int l = 0; l < lanes; ++l) s += red64[(size_t)l * 2 * C + i];
+    dst[i] = s;
   }
 }
 
-// Folds partial[chunks][2][C] into per-channel totals (fp64, fixed order) with the whole block: thread (lane, c4) takes the
+// Forward fold of partial[chunks][2][C] doubles into per-channel totals with half the block's lanes (so that the fp64 scratch is no
+// larger than the backward's fp32 one): thread (lane < lanes / 2, c4) takes the chunks lane, lane + lanes / 2, ... of its four
+// channels, bn_total64 then adds the lanes in order.  Nothing is rounded to fp32.  scratch: [lanes / 2][2][C] doubles.  No more fold
+// lanes than chunks: a small tensor has one or two, and the serial additions of bn_total64 are the kernel's prologue.
+__device__ __forceinline__ int bn_fold_lanes(int lanes, int chunks) { return (lanes >> 1) < chunks ? (lanes >> 1) : chunks; }
+__device__ __forceinline__ void bn_fold_block64(const double* __restrict__ partial, int chunks, int C, int lanes, double* scratch) {
+  const int C4 = C >> 2, fl = bn_fold_lanes(lanes, chunks);
+  const int lane = threadIdx.x / C4, c4 = threadIdx.x - lane * C4;
+  if (lane < fl) {
+    double a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = lane; k < chunks; k += fl) {
+      const double* p = partial + (size_t)k * 2 * C + c4 * 4;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        a[j] += p[j];
+        b[j] += p[C + j];
+      }
+    }
+    double* mine = scratch + (size_t)lane * 2 * C + c4 * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      mine[j] = a[j];
+      mine[C + j] = b[j];
+    }
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ void bn_total64(const double* scratch, int C, int fold_lanes, int c, double& s1, double& s2) {
+  s1 = 0.0; s2 = 0.0;
+  for (int l = 0; l < fold_lanes; ++l) {
+    s1 += scratch[(size_t)(l * 2 + 0) * C + c];
+    s2 += scratch[(size_t)(l * 2 + 1) * C + c];
+  }
+}
+
+// Backward fold of partial[chunks][2][C] floats into per-channel totals (fp64, fixed order) with the whole block: thread (lane, c4) takes the
 // chunks lane, lane+lanes, ... of its four channels (fp64), the lanes are then added in order (fp64).  scratch: [lanes][2][C] floats.
 // On return (after the barrier inside) thread c < C reads its totals with bn_total().
 __device__ __forceinline__ void bn_fold_block(const float* __restrict__ partial, int chunks, int C, int lanes, float* scratch) {
@@ -84,9 +129,11 @@ __device__ __forceinline__ void bn_fold_block(const float* __restrict__ partial,
   }
   __syncthreads();
 }
-__device__ __forceinline__ void bn_total(const float* scratch, int C, int lanes, int c, double& s1, double& s2) {
+// (lanes at and past `chunks` hold zeros: leaving them out gives the same bits)
+__device__ __forceinline__ void bn_total(const float* scratch, int C, int lanes, int chunks, int c, double& s1, double& s2) {
   s1 = 0.0; s2 = 0.0;
-  for (int l = 0; l < lanes; ++l) {
+  const int used = lanes < chunks ? lanes : chunks;
+  for (int l = 0; l < used; ++l) {
     s1 += (double)scratch[(size_t)(l * 2 + 0) * C + c];
     s2 += (double)scratch[(size_t)(l * 2 + 1) * C + c];
   }
@@ -96,21 +143,21 @@ __device__ __forceinline__ void bn_total(const float* scratch, int C, int lanes,
 // add the residual, activate ---------------------------------------------------------------------------------------------
 template <typename T, int ACT, bool RES>
 __global__ __launch_bounds__(BN_NT) void bn_apply_kernel(const T* __restrict__ x, const T* __restrict__ res, long long rows, int C,
-                                                          int lanes, int chunks, const float* __restrict__ partial,
+                                                          int lanes, int chunks, const double* __restrict__ partial,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
                                                           float momentum, float* __restrict__ running_mean, float* __restrict__ running_var,
                                                           float* __restrict__ save_mean, float* __restrict__ save_invstd, int rows_per_block,
                                                           T* __restrict__ out) {
   __shared__ __align__(16) float sc[BN_MAX_C];
   __shared__ __align__(16) float sh[BN_MAX_C];
-  extern __shared__ float fold_scratch[];
-  bn_fold_block(partial, chunks, C, lanes, fold_scratch);
+  extern __shared__ double fold_scratch64[];
+  bn_fold_block64(partial, chunks, C, lanes, fold_scratch64);
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     double s1, s2;
-    bn_total(fold_scratch, C, lanes, c, s1, s2);
+    bn_total64(fold_scratch64, C, bn_fold_lanes(lanes, chunks), c, s1, s2);
     const double n = (double)rows, inv_n = 1.0 / n;
     const double mean = s1 * inv_n;
-    double var = s2 * inv_n - mean * mean;                 // fp64: the cancellation happens here
+    double var = s2 * inv_n - mean * mean;                 // the cancellation: both operands are fp64 sums of exact fp64 terms
     if (var < 0.0) var = 0.0;
     const float invstd = 1.f / sqrtf((float)var + eps);     // fp32 like PyTorch's invstd
     const float k = gamma[c] * invstd;
@@ -121,8 +168,10 @@ __global__ __launch_bounds__(BN_NT) void bn_apply_kernel(const T* __restrict__ x
       save_invstd[c] = invstd;
       if (running_mean) {
         const double unbiased = rows > 1 ? var * n / (n - 1.0) : var;
-        running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-        running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+        // the update in fp64, one rounding on store: within half an fp32 step of the exact update of the fp64 statistics
+        const double mo = (double)momentum;
+        running_mean[c] = (float)((1.0 - mo) * (double)running_mean[c] + mo * mean);
+        running_var[c] = (float)((1.0 - mo) * (double)running_var[c] + mo * unbiased);
       }
     }
   }
@@ -219,7 +268,7 @@ __global__ __launch_bounds__(BN_NT) void bn_bwd_apply_kernel(const T* __restrict
   bn_fold_block(partial, chunks, C, lanes, fold_scratch);
   for (int c = threadIdx.x; c < C; c += blockDim.x) {
     double s1, s2;
-    bn_total(fold_scratch, C, lanes, c, s1, s2);
+    bn_total(fold_scratch, C, lanes, chunks, c, s1, s2);
     mg[c] = (float)(s1 / (double)rows);
     mgx[c] = (float)(s2 / (double)rows);
     if (blockIdx.x == 0) {
@@ -278,7 +327,8 @@ static inline BnPlan bn_plan(long long rows, int C) {
 
 using namespace dd;
 
-extern "C" size_t dd_bn_workspace_bytes(int C) { return (size_t)BN_MAX_CHUNKS * 2 * C * sizeof(float); }
+// the forward's records are doubles, the backward's floats: one size for both
+extern "C" size_t dd_bn_workspace_bytes(int C) { return (size_t)BN_MAX_CHUNKS * 2 * C * sizeof(double); }
 
 #define BN_DISPATCH(KERNEL, ...)                                                                             \
   do {                                                                                                       \
@@ -289,16 +339,17 @@ extern "C" size_t dd_bn_workspace_bytes(int C) { return (size_t)BN_MAX_CHUNKS * 
 
 template <typename T>
 static void bn_fwd_launch(const void* x_, const void* residual_, long long rows, int C, const float* gamma, const float* beta, float eps, float momentum,
-                          float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act, void* out_, float* partial,
+                          float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act, void* out_, double* partial,
                           hipStream_t s) {
   const T* x = static_cast<const T*>(x_);
   const T* residual = static_cast<const T*>(residual_);
   T* out = static_cast<T*>(out_);
   const BnPlan p = bn_plan(rows, C);
-  const size_t lds = (size_t)p.g.lanes * 2 * C * sizeof(float);
-  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(p.chunks), dim3(p.g.threads), lds, s, x, rows, C, p.g.lanes, p.rows_per_chunk, partial);
+  const size_t lds_stats = (size_t)p.g.lanes * 2 * C * sizeof(double);            // <= 64 KB: lanes * C <= 4096
+  const size_t lds_fold = (size_t)(p.g.lanes >> 1) * 2 * C * sizeof(double);       // lanes >= 8 as C <= 512
+  hipLaunchKernelGGL(bn_stats_kernel<T>, dim3(p.chunks), dim3(p.g.threads), lds_stats, s, x, rows, C, p.g.lanes, p.rows_per_chunk, partial);
   const bool has_res = residual != nullptr;
-  BN_DISPATCH(bn_apply_kernel, <<<dim3(p.blocks), dim3(p.g.threads), lds, s>>>(x, residual, rows, C, p.g.lanes, p.chunks, partial, gamma, beta, eps,
+  BN_DISPATCH(bn_apply_kernel, <<<dim3(p.blocks), dim3(p.g.threads), lds_fold, s>>>(x, residual, rows, C, p.g.lanes, p.chunks, partial, gamma, beta, eps,
                                                                              momentum, running_mean, running_var, save_mean, save_invstd,
                                                                              p.rows_per_block, out));
 }
@@ -343,10 +394,11 @@ extern "C" int dd_bn_act_fwd_t(const void* x, const void* residual, long long ro
                                void* out, int dtype, void* workspace, size_t workspace_bytes, void* stream) {
   if (!x || !gamma || !beta || !save_mean || !save_invstd || !out || !workspace || !bn_dims_ok(rows, C) || act < 0 || act > 2 || dtype < 0 || dtype > 2)
     return (int)hipErrorInvalidValue;
-  if (workspace_bytes < dd_bn_workspace_bytes(C) || (running_mean == nullptr) != (running_var == nullptr)) return (int)hipErrorInvalidValue;
+  if (workspace_bytes < dd_bn_workspace_bytes(C) || (reinterpret_cast<size_t>(workspace) & 7) || (running_mean == nullptr) != (running_var == nullptr))
+    return (int)hipErrorInvalidValue;
   if (act == BN_ACT_GELU && residual) return (int)hipErrorInvalidValue;          // not a combination of the reference's networks
   DD_DISPATCH_DTYPE(dtype, bn_fwd_launch, x, residual, rows, C, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, act, out,
-                    static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
+                    static_cast<double*>(workspace), static_cast<hipStream_t>(stream));
   return (int)hipGetLastError();
 }
 

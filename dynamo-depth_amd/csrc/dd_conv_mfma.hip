@@ -229,7 +229,7 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const float* __restric
   // Software pipeline.  The fragments of step s + 1 are read into a second register set and the weights of step s + 2 are fetched into
   // the buffer step s has finished with WHILE the MFMAs of step s run; the barrier at the end of a step finds everything in place.
   uint4 af[2][2][3], bfr[2][NB][3];
-  auto read_frags = [&](int set, int tap, int s) {
+  auto read_a = [&](int set, int tap) {
     const int ty = tap / 3, tx = tap % 3;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -237,11 +237,17 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const float* __restric
 #pragma unroll
       for (int pc = 0; pc < pieces_of(NP); ++pc) af[set][m][pc] = *reinterpret_cast<const uint4*>(ap + pc * A_PIECE);
     }
+  };
+  auto read_b = [&](int set, int s) {
     const unsigned char* bb = b_lane + (s & 1) * b_buf_bytes<NB>();
 #pragma unroll
     for (int n = 0; n < NB; ++n)
 #pragma unroll
       for (int pc = 0; pc < pieces_of(NP); ++pc) bfr[set][n][pc] = *reinterpret_cast<const uint4*>(bb + (n * 3 + pc) * FRAG);
+  };
+  auto read_frags = [&](int set, int tap, int s) {
+    read_a(set, tap);
+    read_b(set, s);
   };
 
   const int nsteps = nchunks * 9;
@@ -255,10 +261,15 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_kernel(const float* __restric
   fetch_b(1);                              // nsteps >= 9
   for (int chunk = 0; chunk < nchunks; ++chunk) {
     lds_barrier();                         // the previous chunk's fragment reads are done
+    // The weights of the chunk's first step went in one step earlier and are read HERE, in front of the barrier below: the first tap
+    // ends with store_b(s + 2) into this very buffer and has no barrier in front of it, so a wave that read them behind that barrier
+    // could find the fragments of step s + 2 that a faster wave had already stored (one step of 16 channels with the wrong weights;
+    // seen with one partial product per step, where a tap is four MFMAs long).
+    read_b(0, chunk * 9);
     stage(chunk);
-    store_b(chunk * 9 + 1);                // the weights of the chunk's second step (its first step's went in one step earlier)
+    store_b(chunk * 9 + 1);                // the weights of the chunk's second step
     lds_barrier();
-    read_frags(0, 0, chunk * 9);
+    read_a(0, 0);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int s = chunk * 9 + tap, cur = tap & 1;
@@ -411,7 +422,7 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_flat_kernel(const float* __re
   const unsigned char* b_lane = s_b + lane * 16;
 
   uint4 af[2][2][3], bfr[2][NB][3];
-  auto read_frags = [&](int set, int tap, int s) {
+  auto read_a = [&](int set, int tap) {
     const int toff = (tap / 3 - 1) * W + (tap % 3 - 1);                  // wave-uniform, in pixels
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -419,11 +430,17 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_flat_kernel(const float* __re
 #pragma unroll
       for (int pc = 0; pc < pieces_of(NP); ++pc) af[set][m][pc] = *reinterpret_cast<const uint4*>(smem + addr + pc * A_PIECE);
     }
+  };
+  auto read_b = [&](int set, int s) {
     const unsigned char* bb = b_lane + (s & 1) * b_buf_bytes<NB>();
 #pragma unroll
     for (int n = 0; n < NB; ++n)
 #pragma unroll
       for (int pc = 0; pc < pieces_of(NP); ++pc) bfr[set][n][pc] = *reinterpret_cast<const uint4*>(bb + (n * 3 + pc) * FRAG);
+  };
+  auto read_frags = [&](int set, int tap, int s) {
+    read_a(set, tap);
+    read_b(set, s);
   };
 
   const int s_last = c_end * 9 - 1;
@@ -436,10 +453,11 @@ __global__ __launch_bounds__(NT, 2) void conv_mfma_flat_kernel(const float* __re
   fetch_b(min(c_begin * 9 + 1, s_last));
   for (int chunk = c_begin; chunk < c_end; ++chunk) {
     lds_barrier();
+    read_b(0, chunk * 9);                  // in front of the barrier below, as in conv_mfma_kernel: the first tap's store_b(s + 2) overwrites this buffer
     stage(chunk);
     store_b(chunk * 9 + 1);
     lds_barrier();
-    read_frags(0, 0, chunk * 9);
+    read_a(0, 0);
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int s = chunk * 9 + tap, cur = tap & 1;
