@@ -19,6 +19,7 @@
 //     stores straight-line, edge tiles test every store.
 // Bound: HBM for the wide side (the 6C-wide tensor is written or read once, 4 bytes per element).
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <type_traits>
 
 #include "../../include/dynamo_hip.h"
@@ -430,10 +431,27 @@ constexpr int BR3 = (NF3 + 3) / 4;
 constexpr int MLP3_LDS = 2 * NF3 * FRAG + 6 * C3 * 4;           // W1 block | W2 block | b1
 static_assert(NF3 == NB3 * 6, "both operands of a hidden block have the same number of fragments");
 
-template <int NP>
+//
+// MODE (the training pass): the same loop with what the slices do exchanged.
+//   MLP_TRAIN  the forward of a pass with a tape: besides the output, h = GELU(pre) and d = GELU'(pre) (M, 1344) go to memory straight from
+//              the accumulator's slices -- registers 4 q .. 4 q + 3 of a lane are sixteen contiguous bytes of its pixel's row, lanes l and
+//              l + 32 complete 32 -- so the backward needs no activation arithmetic.  The arithmetic of the output is MLP_FWD's, bit for bit.
+//   MLP_DGRAD  the data gradient dx = ((g . W2) * d) . W1: x = g, pack1 = W2^T as first operand, pack2 = W1^T in fused-k order, no bias and
+//              no GELU: the slice multiplies the accumulator by the d tile and stores gpre = (g . W2) * d (dd_linear_wgrad's operand),
+//              which is also the second GEMM's A operand.  The d tile (4 KB per wave and hidden block) comes global -> LDS one block ahead
+//              (four global_load_lds_dwordx4 per wave, per-lane addresses, two buffers per wave) and is read back in accumulator layout.
+// Rows at or beyond M are never stored (their x rows are clamped).  A (row group, hidden block) pair belongs to one split: no fold.
+// Stores count in vmcnt, in order, and wait_barrier() waits for all of them: the stores of h and gpre go out from the slices right BEHIND
+// the mid-block barrier (the values are held for the split anyway), those of d when a quad is complete (at 252 VGPRs there is no room to
+// hold them).
+constexpr int MLP_FWD = 0, MLP_TRAIN = 1, MLP_DGRAD = 2;
+constexpr int MLP3_DTILE = 4096;                                // one wave's d tile of a hidden block: 32 pixels x 32 hidden units
+
+template <int NP, int MODE>
 __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restrict__ x, const uint4* __restrict__ pack1, const uint4* __restrict__ pack2,
                                                             const float* __restrict__ b1, const float* __restrict__ bias, int M, int S,
-                                                            float* __restrict__ dst) {
+                                                            float* __restrict__ dst, const float* __restrict__ aux_in, float* __restrict__ out_a,
+                                                            float* __restrict__ out_b) {
   extern __shared__ __align__(16) unsigned char smem[];
   unsigned char* const s_w1 = smem;
   unsigned char* const s_w2 = smem + NF3 * FRAG;
@@ -441,8 +459,13 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6) & 3, hh = lane >> 5;
   const int row0 = (int)blockIdx.x * 128 + wave * 32;
   const int split = (int)blockIdx.y, hb0 = split * NHB3 / S, hb1 = (split + 1) * NHB3 / S;
+  // this lane's pixel in the (M, 1344) tensors: element offset of its hidden unit 4 hh (the host keeps M * 1344 * 4 below 2^32)
+  const bool row_ok = row0 + (lane & 31) < M;
+  const unsigned aoff = (unsigned)min(row0 + (lane & 31), M - 1) * (unsigned)(6 * C3) + 4u * hh;
+  const unsigned char* const s_d = smem + MLP3_LDS + wave * 2 * MLP3_DTILE + lane * 16;       // MLP_DGRAD: this wave's two d tiles
 
-  for (int i = tid; i < 6 * C3; i += 256) s_b1[i] = b1[i];
+  if (MODE != MLP_DGRAD)
+    for (int i = tid; i < 6 * C3; i += 256) s_b1[i] = b1[i];
   uint4 xf[KS3][3];
   {
     const float* xp = x + (size_t)min(row0 + (lane & 31), M - 1) * C3 + hh * 8;
@@ -463,7 +486,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   // fragments w, w + 4, ...  The compiler does not count these loads: wait_barrier() waits for them, and nothing reads a buffer
   // between its dma() and the next wait_barrier().
   const unsigned lds0 = (unsigned)reinterpret_cast<size_t>(smem);
-  auto dma = [&](const uint4* pack, int hb, unsigned char* s_w) {
+  auto dma = [&](const uint4* pack, int hb, unsigned char* s_w) __attribute__((always_inline)) {
     const uint4* src = pack + (size_t)hb * (NF3 * 64) + lane;
 #pragma unroll
     for (int r = 0; r < BR3; ++r) {
@@ -474,8 +497,21 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
                    : "=&s"(keep) : "v"(src + f * 64), "s"(dst) : "memory");
     }
   };
+  // MLP_DGRAD: this wave's d tile of hidden block hb -> its buffer `buf`, in accumulator layout: instruction q moves, for every lane, the
+  // four hidden units 8 q + 4 hh .. + 3 of its pixel (the accumulator's registers 4 q .. 4 q + 3) to byte q * 1024 + 16 lane.  Only this
+  // wave reads the tile; like dma() it is complete after the next wait_barrier().
+  auto dma_d = [&](int hb, int buf) __attribute__((always_inline)) {
+    const float* src = aux_in + aoff + hb * 32;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(MLP3_LDS + (wave * 2 + buf) * MLP3_DTILE + q * FRAG));
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep) : "v"(src + 8 * q), "s"(dst) : "memory");
+    }
+  };
   // every load and LDS operation of this wave has completed (the weight fragments it moved have landed), then the barrier
-  auto wait_barrier = [&]() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+  auto wait_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
   // One scheduling region per MFMA step (six products on one pair of fragments): the step's MFMAs, the LDS reads of the NEXT step's
   // weight fragments, and one slice of the activation's VALU work.  (Left to itself the scheduler hoists the fragment reads of a whole
@@ -485,7 +521,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   for (int n = 0; n < NB3; ++n)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc2[n][r] = 0.f;
-  auto read_w = [&](const unsigned char* s_w, int f, uint4 (&wf)[3]) {
+  auto read_w = [&](const unsigned char* s_w, int f, uint4 (&wf)[3]) __attribute__((always_inline)) {
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc) wf[pc] = *reinterpret_cast<const uint4*>(s_w + lane * 16 + (f * 3 + pc) * FRAG);
   };
@@ -493,13 +529,42 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   // the split into the second GEMM's A fragments (registers 8 j .. 8 j + 7 are step j), in 21 slices: 0..10 and 14..18 one GELU each,
   // 11, 12 the fragments of step 0, 19, 20 those of step 1 -- fourteen slices beside the first GEMM of the next block, seven beside
   // step 0 of the second GEMM
+  // MLP_TRAIN / MLP_DGRAD: the quads of hv (h, or gpre) are stored from slices 14, 15, 16 and 19, behind the mid-block barrier; d's quad
+  // q when its last value exists (slices 3, 7, 14, 18); MLP_DGRAD reads quad q of the d tile in the slice of its first register
   float hv[16];
+  float dv[4];
   uint4 hf[2][3];
-  auto slice = [&](const f16v& acc, int hb, int i) {
+  int dbuf = 0;                                      // MLP_DGRAD: the buffer that holds the d tile of the block the slices work on
+  auto store_quad = [&](float* __restrict__ out, int hb, int q, const float* v) __attribute__((always_inline)) {
+    if (row_ok) *reinterpret_cast<float4*>(out + aoff + hb * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+  };
+  auto slice = [&](const f16v& acc, int hb, int i) __attribute__((always_inline)) {
     const int r = i < 11 ? i : i - 3;
     if (i < 11 || (i >= 14 && i < 19)) {
-      hv[r] = gelu_erf(acc[r] + s_b1[hb * 32 + 8 * (r >> 2) + 4 * hh + (r & 3)]);
+      if (MODE == MLP_DGRAD) {
+        if ((r & 3) == 0) {
+          const float4 dq = *reinterpret_cast<const float4*>(s_d + dbuf * MLP3_DTILE + (r >> 2) * FRAG);
+          dv[0] = dq.x; dv[1] = dq.y; dv[2] = dq.z; dv[3] = dq.w;
+        }
+        hv[r] = acc[r] * dv[r & 3];
+      } else {
+        const float v = acc[r] + s_b1[hb * 32 + 8 * (r >> 2) + 4 * hh + (r & 3)];
+        if (MODE == MLP_TRAIN) {                     // gelu_erf's arithmetic for h, gelu_pair_kernel's for d
+          const float er = 1.f + erf_poly(v * 0.70710678118654752440f);
+          const float pdf = __expf(-0.5f * v * v) * 0.3989422804014327f;
+          hv[r] = (v * 0.5f) * er;
+          dv[r & 3] = fmaf(v, pdf, 0.5f * er);
+          asm volatile("" : "+v"(dv[r & 3]));
+        } else {
+          hv[r] = gelu_erf(v);
+        }
+      }
       asm volatile("" : "+v"(hv[r]));              // computed HERE, beside this step's MFMAs (else it sinks to its first use)
+      if (MODE == MLP_TRAIN && (r & 3) == 3) store_quad(out_b, hb, r >> 2, dv);
+    }
+    if (MODE != MLP_FWD && (i == 14 || i == 15 || i == 16 || i == 19)) {
+      const int q = i == 19 ? 3 : i - 14;
+      store_quad(out_a, hb, q, hv + 4 * q);
     }
     if (i == 11 || i == 12 || i == 19 || i == 20) {
       const int j = i >= 19, q0 = (i == 12 || i == 20) ? 2 : 0;
@@ -517,7 +582,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
     }
   };
   // first GEMM, transposed: h^T (32 hidden x 32 pixels) = W1 block . x^T, with slices 0..13 of block hb's activation when `act`
-  auto gemm1 = [&](f16v& acc, const f16v& prev, int hb, auto act) {
+  auto gemm1 = [&](f16v& acc, const f16v& prev, int hb, auto act) __attribute__((always_inline)) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     uint4 wf[2][3];
@@ -533,7 +598,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
     }
   };
   // second GEMM: out (32 pixels x 224) += h (A operand, straight from the registers) . W2 block, with slices 14..20 beside step 0
-  auto gemm2 = [&](const f16v& prev, int hb) {
+  auto gemm2 = [&](const f16v& prev, int hb) __attribute__((always_inline)) {
     uint4 wf[2][3];
     read_w(s_w2, 0, wf[0]);
 #pragma unroll
@@ -555,6 +620,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   // prologue: W1 of the first block, its first GEMM, then W1 of the second block in place and W2 of the first one on its way
   f16v acc1;
   dma(pack1, hb0, s_w1);
+  if (MODE == MLP_DGRAD) dma_d(hb0, 0);
   wait_barrier();                                  // (b1 is in place too)
   gemm1(acc1, acc1, hb0, std::false_type{});
   wait_barrier();                                  // every wave has read W1 of the first block
@@ -562,8 +628,9 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   wait_barrier();
   dma(pack2, hb0, s_w2);
   // here, for every hb: acc1 = the pre-activation of block hb less its bias, s_w1 = W1 of block hb + 1, W2 of block hb on its way to s_w2
-  auto block = [&](int hb, auto more) {
+  auto block = [&](int hb, auto more) __attribute__((always_inline)) {
     f16v accn;
+    dbuf = (hb - hb0) & 1;
     if (decltype(more)::value) gemm1(accn, acc1, hb, std::true_type{});        // block hb + 1, beside the VALU work of block hb
     else {
 #pragma unroll
@@ -571,6 +638,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
     }
     wait_barrier();                                // W2 of block hb is in place, every wave has read s_w1
     if (decltype(more)::value) dma(pack1, min(hb + 2, hb1 - 1), s_w1);
+    if (MODE == MLP_DGRAD && decltype(more)::value) dma_d(hb + 1, dbuf ^ 1);   // the other buffer: slices 14..18 still read this one
     gemm2(acc1, hb);
     if (decltype(more)::value) {
       wait_barrier();                              // W1 of block hb + 2 is in place, every wave has read s_w2
@@ -583,7 +651,7 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   block(hb1 - 1, std::false_type{});
 
   float* const out = dst + (size_t)split * M * C3;
-  auto tail = [&](auto full) {
+  auto tail = [&](auto full) __attribute__((always_inline)) {
     const int row = row0 + 4 * hh;
 #pragma unroll
     for (int n = 0; n < NB3; ++n)
@@ -593,11 +661,11 @@ __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restr
   else tail(std::false_type{});
 }
 
-// y = b2 + partial 0 + partial 1 + ... in that order, four channels per thread (224 = 56 quads per row)
+// y = b2 + partial 0 + partial 1 + ... in that order, four channels per thread (224 = 56 quads per row); the data gradient has no b2
 __global__ __launch_bounds__(256) void mlp_fold224_kernel(const float4* __restrict__ partial, const float4* __restrict__ b2, int S, size_t quads, float4* __restrict__ y) {
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= quads) return;
-  float4 a = b2[i % (C3 / 4)];
+  float4 a = b2 ? b2[i % (C3 / 4)] : make_float4(0.f, 0.f, 0.f, 0.f);
   for (int s = 0; s < S; ++s) {
     const float4 p = partial[(size_t)s * quads + i];
     a.x += p.x; a.y += p.y; a.z += p.z; a.w += p.w;
@@ -612,14 +680,17 @@ static int mlp224_splits(int M) {
   return n < 1 ? 1 : n > NHB3 ? NHB3 : n;
 }
 
-template <int NP>
+// MLP_FWD / MLP_TRAIN: y = the block's output (out_a = h, out_b = d for MLP_TRAIN).  MLP_DGRAD: x = g, aux_in = d, pack1 = W2^T, pack2 =
+// W1^T fused, b1 = b2 = nullptr, y = dx, out_a = gpre.
+template <int NP, int MODE>
 static int launch_fused224(const float* x, const void* pack1, const void* pack2, const float* b1, const float* b2, int M, int S, float* y, float* partial,
-                           hipStream_t stream) {
-  auto kern = mlp_fwd224_kernel<NP>;
+                           hipStream_t stream, const float* aux_in = nullptr, float* out_a = nullptr, float* out_b = nullptr) {
+  constexpr int lds = MLP3_LDS + (MODE == MLP_DGRAD ? 4 * 2 * MLP3_DTILE : 0);      // two d tiles per wave
+  auto kern = mlp_fwd224_kernel<NP, MODE>;
   static dd::LdsAttrOnce lds_attr;          // per instantiation and device (dd_attr.h)
-  if (const int rc = lds_attr.ensure(reinterpret_cast<const void*>(kern), MLP3_LDS)) return rc;
-  hipLaunchKernelGGL(kern, dim3((M + 127) / 128, S), dim3(256), MLP3_LDS, stream, x, static_cast<const uint4*>(pack1), static_cast<const uint4*>(pack2), b1,
-                     S == 1 ? b2 : nullptr, M, S, S == 1 ? y : partial);
+  if (const int rc = lds_attr.ensure(reinterpret_cast<const void*>(kern), lds)) return rc;
+  hipLaunchKernelGGL(kern, dim3((M + 127) / 128, S), dim3(256), lds, stream, x, static_cast<const uint4*>(pack1), static_cast<const uint4*>(pack2), b1,
+                     S == 1 ? b2 : nullptr, M, S, S == 1 ? y : partial, aux_in, out_a, out_b);
   if (S == 1) return (int)hipGetLastError();
   const size_t quads = (size_t)M * (C3 / 4);
   hipLaunchKernelGGL(mlp_fold224_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, reinterpret_cast<const float4*>(partial),
@@ -678,6 +749,74 @@ extern "C" int dd_mlp_pack(const float* w1, long long s1_n, long long s1_k, cons
   return (int)hipGetLastError();
 }
 
+// ---- the training pass of the stage-3 block (C = 224): forward that saves h and d, fused data gradient ------------------------------
+extern "C" int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
+                                 void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream) {
+  using namespace dd::pw;
+  if (!w1 || !w2 || C != C3 || hidden != 6 * C3 || !pack_fwd1 || !pack_fwd2_fused || !pack_bwd2 || !pack_bwd1_fused) return (int)hipErrorInvalidValue;
+  PackArgs a;
+  a.count = 0;
+  a.total = 0;
+  auto add = [&](const float* w, long long s_n, long long s_k, int N, int K, void* out, int fused) {
+    PackRegion& r = a.r[a.count++];
+    r.w = w; r.s_n = s_n; r.s_k = s_k; r.N = N; r.K = K; r.first = a.total; r.fused = fused; r.out = static_cast<uint4*>(out);
+    a.total += ((N + 31) / 32) * (K / 16);
+  };
+  add(w1, s1_n, s1_k, hidden, C, pack_fwd1, 0);        // pre = x . W1^T: first operand of the forward
+  add(w2, s2_n, s2_k, C, hidden, pack_fwd2_fused, 1);  // W2 by hidden block, k in accumulator-register order
+  add(w2, s2_k, s2_n, hidden, C, pack_bwd2, 0);        // g . W2: W2^T (n = hidden, k = C) as the data gradient's first operand
+  add(w1, s1_k, s1_n, C, hidden, pack_bwd1_fused, 1);  // . W1: W1^T (n = C, k = hidden) by hidden block, fused-k order
+  for (int i = a.count; i < MAX_REGIONS; ++i) a.r[i] = a.r[0];
+  hipLaunchKernelGGL(pw_pack_kernel, dim3((a.total * 64 + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return (int)hipGetLastError();
+}
+
+extern "C" size_t dd_mlp_train_bwd_workspace_bytes(int M, int C, int splits) {
+  if (M < 1 || C != dd::pw::C3 || splits < 0 || splits > dd::pw::NHB3) return 0;
+  const int S = splits ? splits : dd::pw::mlp224_splits(M);
+  return S > 1 ? (size_t)S * M * C * sizeof(float) : 0;
+}
+
+// what both training entry points refuse: another width, rows whose (M, 1344) tensors pass 2^32 bytes (the kernel's 32-bit offsets),
+// more splits than hidden blocks, an unknown product count
+static bool mlp_train_shape_ok(int M, int C, int products, int splits) {
+  return C == dd::pw::C3 && M >= 1 && M <= (1 << 19) && splits >= 0 && splits <= dd::pw::NHB3 && (products == 6 || products == 3 || products == 1);
+}
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+  unsigned long long bits = 0;
+  for (const void* p : ps) bits |= reinterpret_cast<unsigned long long>(p);
+  return (bits & 15ull) == 0;
+}
+
+extern "C" int dd_mlp_train_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C,
+                                int products, int splits, float* y, float* h, float* d, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace dd::pw;
+  if (!x || !pack_fwd1 || !pack_fwd2_fused || !b1 || !b2 || !y || !h || !d || !mlp_train_shape_ok(M, C, products, splits)) return (int)hipErrorInvalidValue;
+  if (!aligned16({x, y, h, d, b2, workspace, pack_fwd1, pack_fwd2_fused})) return (int)hipErrorInvalidValue;
+  const int S = splits ? splits : mlp224_splits(M);
+  if (S > 1 && (!workspace || workspace_bytes < dd_mlp_fwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  return products == 6 ? launch_fused224<6, MLP_TRAIN>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s, nullptr, h, d)
+       : products == 3 ? launch_fused224<3, MLP_TRAIN>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s, nullptr, h, d)
+                       : launch_fused224<1, MLP_TRAIN>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s, nullptr, h, d);
+}
+
+extern "C" int dd_mlp_train_bwd(const float* g, const float* d, const void* pack_bwd2, const void* pack_bwd1_fused, int M, int C, int products, int splits,
+                                float* dx, float* gpre, void* workspace, size_t workspace_bytes, void* stream) {
+  using namespace dd::pw;
+  if (!g || !d || !pack_bwd2 || !pack_bwd1_fused || !dx || !gpre || !mlp_train_shape_ok(M, C, products, splits)) return (int)hipErrorInvalidValue;
+  if (!aligned16({g, d, dx, gpre, workspace, pack_bwd2, pack_bwd1_fused})) return (int)hipErrorInvalidValue;
+  const int S = splits ? splits : mlp224_splits(M);
+  if (S > 1 && (!workspace || workspace_bytes < dd_mlp_train_bwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  float* part = static_cast<float*>(workspace);
+  return products == 6 ? launch_fused224<6, MLP_DGRAD>(g, pack_bwd2, pack_bwd1_fused, nullptr, nullptr, M, S, dx, part, s, d, gpre, nullptr)
+       : products == 3 ? launch_fused224<3, MLP_DGRAD>(g, pack_bwd2, pack_bwd1_fused, nullptr, nullptr, M, S, dx, part, s, d, gpre, nullptr)
+                       : launch_fused224<1, MLP_DGRAD>(g, pack_bwd2, pack_bwd1_fused, nullptr, nullptr, M, S, dx, part, s, d, gpre, nullptr);
+}
+
 extern "C" int dd_mlp_fwd_supported(int C) { return (C == 64 || C == 128 || C == 224) ? 1 : 0; }
 
 extern "C" int dd_mlp_fwd_splits(int M, int C) { return (C == dd::pw::C3 && M >= 1) ? dd::pw::mlp224_splits(M) : 1; }
@@ -701,9 +840,9 @@ extern "C" int dd_mlp_fwd_n(const float* x, const void* pack_fwd1, const void* p
   if (S > 1 && (!workspace || workspace_bytes < dd_mlp_fwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   float* part = static_cast<float*>(workspace);
-  return products == 6 ? launch_fused224<6>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
-       : products == 3 ? launch_fused224<3>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
-                       : launch_fused224<1>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s);
+  return products == 6 ? launch_fused224<6, MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
+       : products == 3 ? launch_fused224<3, MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s)
+                       : launch_fused224<1, MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, S, y, part, s);
 }
 
 extern "C" int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, float* y, void* stream) {
@@ -712,7 +851,7 @@ extern "C" int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pac
   switch (C) {
     case 64: return dd::pw::launch_fused<64>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
     case 128: return dd::pw::launch_fused<128>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
-    case 224: return dd::pw::launch_fused224<6>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, 1, y, nullptr, s);      // unsplit: dd_mlp_fwd_n fills the chip
+    case 224: return dd::pw::launch_fused224<6, dd::pw::MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, 1, y, nullptr, s);      // unsplit: dd_mlp_fwd_n fills the chip
     default: return (int)hipErrorInvalidValue;
   }
 }

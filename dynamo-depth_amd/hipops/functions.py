@@ -1161,6 +1161,85 @@ def mlp_recompute(y, block):
     return MlpRecomputeFn.apply(y, block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias)
 
 
+_MLP_TRAIN_CALLS = [0]
+
+# rows from which the stage-3 training pass (forward + backward) is ahead of the library's: the per-shape table of profiles/mlp_stage3_train.txt
+_MLP_TRAIN_MIN_ROWS = 1920
+
+
+def mlp_train_calls():
+    """How many TRAINING block forwards MlpTrainFn has run through dd_mlp_train_fwd in this process."""
+    return _MLP_TRAIN_CALLS[0]
+
+
+def mlp_train_ok(y, block):
+    """The training pass of this block takes MlpTrainFn: tape on, fp32, no autocast, C = 224 with the 6x expansion and the erf GELU,
+    contiguous (B,H,W,C), rows from _MLP_TRAIN_MIN_ROWS (DD_MLP_TRAIN_MIN_ROWS overrides it).  DD_MLP_TRAIN=0 or DD_STOCK_MLP=1 turn it off."""
+    if (not torch.is_grad_enabled() or os.environ.get("DD_MLP_TRAIN", "1") != "1" or os.environ.get("DD_STOCK_MLP", "0") == "1"
+            or torch.is_autocast_enabled()):
+        return False
+    l1, l2 = block.pwconv1, block.pwconv2
+    if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and y.shape[-1] == 224
+            and l1.weight.dtype == torch.float32 and l2.weight.dtype == torch.float32):
+        return False
+    min_rows = os.environ.get("DD_MLP_TRAIN_MIN_ROWS")
+    if y.shape[0] * y.shape[1] * y.shape[2] < (int(min_rows) if min_rows is not None else _MLP_TRAIN_MIN_ROWS):
+        return False
+    return bool(l1.bias is not None and l2.bias is not None and l1.in_features == 224 and l1.out_features == 6 * 224
+                and l2.in_features == l1.out_features and l2.out_features == 224 and isinstance(block.act, torch.nn.GELU)
+                and getattr(block.act, "approximate", "none") == "none")
+
+
+class MlpTrainFn(torch.autograd.Function):
+    """pwconv2(GELU(pwconv1(y))) of a stage-3 LiteMono block (C = 224) in a TRAINING pass (reference networks/depth_encoder.py:200-203,
+    216-224,262-272), csrc/dd_pw_gemm.hip.  Forward: dd_mlp_train_pack (one launch, four operands), then dd_mlp_fwd_n's kernel, which also
+    stores h = GELU(pre) and d = GELU'(pre) from its accumulator; the pre-activation is never written.  Backward: dd_mlp_train_bwd gives
+    dx = ((g . w2) * d) . w1 in one kernel and stores gpre = (g . w2) * d, then _mlp_param_grads (dd_linear_wgrad) on (gpre, y) and (g, h).
+    Six library launches and ~280 MB per block become two kernels, their folds and ~125 MB; everything is bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, y, w1, b1, w2, b2):
+        lib = L.load()
+        B, H, W, Cc = y.shape
+        hid, M = w1.shape[0], B * H * W
+        nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)          # all four operands have hidden x C elements
+        packs = torch.empty(nb, dtype=torch.float32, device=y.device)      # fwd1 | fwd2 fused | bwd2 | bwd1 fused
+        p0, stream = packs.data_ptr(), L.current_stream()
+        L.check(lib.dd_mlp_train_pack(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, p0 + nb, p0 + 2 * nb,
+                                      p0 + 3 * nb, stream), "dd_mlp_train_pack")
+        out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
+        h = torch.empty((M, hid), dtype=torch.float32, device=y.device)
+        d = torch.empty((M, hid), dtype=torch.float32, device=y.device)
+        nbytes = _ws_bytes("dd_mlp_fwd_workspace_bytes", M, Cc, 0)
+        ws = _ws(nbytes, y.device)
+        L.check(lib.dd_mlp_train_fwd(_p(y), p0, p0 + nb, _p(b1), _p(b2), M, Cc, mfma_products(), 0, _p(out), _p(h), _p(d), _p(ws), nbytes, stream),
+                "dd_mlp_train_fwd")
+        _MLP_TRAIN_CALLS[0] += 1
+        ctx.save_for_backward(y, h, d, w1, w2, packs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        y, h, d, w1, w2, packs = ctx.saved_tensors
+        lib = L.load()
+        B, H, W, Cc = y.shape
+        hid, M = w1.shape[0], B * H * W
+        nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)
+        p0, stream = packs.data_ptr(), L.current_stream()
+        g = g.to(torch.float32).contiguous()
+        gy = torch.empty((B, H, W, Cc), dtype=torch.float32, device=g.device)
+        gpre = torch.empty((M, hid), dtype=torch.float32, device=g.device)
+        nbytes = _ws_bytes("dd_mlp_train_bwd_workspace_bytes", M, Cc, 0)
+        ws = _ws(nbytes, g.device)
+        L.check(lib.dd_mlp_train_bwd(_p(g), _p(d), p0 + 2 * nb, p0 + 3 * nb, M, Cc, mfma_products(), 0, _p(gy), _p(gpre), _p(ws), nbytes, stream),
+                "dd_mlp_train_bwd")
+        return (gy if ctx.needs_input_grad[0] else None,) + _mlp_param_grads(ctx.needs_input_grad, g, gpre, y, h, w1, w2, B, H, W, stream)
+
+
+def mlp_train(y, block):
+    return MlpTrainFn.apply(y, block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias)
+
+
 BN_ACTS = {None: 0, "relu": 1, "gelu": 2}
 
 

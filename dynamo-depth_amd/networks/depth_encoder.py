@@ -223,10 +223,13 @@ def _mlp_residual(block, y, res):
     residual are one addcmul instead of three element-wise passes."""
     B, H, W, Cc = y.shape
     if y.is_cuda and os.environ.get("DD_STOCK_LINEAR_GRAD", "0") != "1":
-        from hipops.functions import mlp, mlp_fused, mlp_fused_ok, mlp_ok, mlp_recompute, mlp_recompute_ok, pointwise_linear
+        from hipops.functions import (mlp, mlp_fused, mlp_fused_ok, mlp_ok, mlp_recompute, mlp_recompute_ok, mlp_train, mlp_train_ok,
+                                      pointwise_linear)
         y = y.contiguous()
         if mlp_fused_ok(y, block):
             y = mlp_fused(y, block)                            # forward-only pass: the whole block in one kernel, hidden tile on chip
+        elif mlp_train_ok(y, block):
+            y = mlp_train(y, block)                            # stage 3 with a tape: the same kernel saves GELU and GELU', fused data gradient
         elif mlp_recompute_ok(y, block):
             y = mlp_recompute(y, block)                        # training pass: the same kernel forward, the hidden tensor rebuilt in the backward
         elif mlp_ok(y, block):

@@ -692,6 +692,27 @@ int dd_mlp_fwd_n(const float* x, const void* pack_fwd1, const void* pack_fwd2_fu
 int dd_pw_gemm(const float* x, const void* pack, const float* bias, int M, int K, int N, int gelu_in, float* y, void* stream);
 int dd_gelu_pair(const float* pre, float* g_inout, float* post, size_t n, void* stream);
 
+/* The TRAINING pass of the stage-3 block (reference networks/depth_encoder.py:200-203,216-224,262-272 at C = 224, hidden 1344: pwconv1 ->
+ * GELU -> pwconv2 with a tape, and its data gradient) in dd_mlp_fwd_n's kernel (csrc/dd_pw_gemm.hip: mlp_fwd224_kernel, MLP_TRAIN / MLP_DGRAD).
+ * dd_mlp_train_pack: ONE launch writes the four operands a training block needs, each dd_pw_gemm_pack_bytes(hidden, C) bytes, 16-byte
+ * aligned: pack_fwd1 and pack_fwd2_fused as dd_mlp_pack writes them, pack_bwd2 = w2 transposed as a first operand (n = hidden, k = C) and
+ * pack_bwd1_fused = w1 transposed by hidden block in the accumulator's contraction order (n = C, k = hidden).
+ * dd_mlp_train_fwd: y (M,224) = GELU(x . w1^T + b1) . w2^T + b2 exactly as dd_mlp_fwd_n computes it (bit-identical for the same products and
+ * splits; workspace dd_mlp_fwd_workspace_bytes), and beside it h = GELU(pre) and d = GELU'(pre) (M,1344 each, dense, 16-byte aligned),
+ * stored from the first GEMM's accumulator; rows at or beyond M are never written.
+ * dd_mlp_train_bwd: dx (M,224) = ((g . w2) * d) . w1 in one kernel and gpre (M,1344) = (g . w2) * d, the operand of the first Linear's
+ * weight gradient (dd_linear_wgrad); the hidden range is split as in the forward, the partials (dd_mlp_train_bwd_workspace_bytes(M, C,
+ * splits) bytes, 16-byte aligned, private to the call's stream) folded in split order: no atomics, no zero-fill, bit-reproducible for a
+ * given split count.  All three refuse C != 224; the two kernels refuse M > 2^19, splits > 42, a short workspace, a pointer that is not
+ * 16-byte aligned and products outside {6, 3, 1}. */
+int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden, void* pack_fwd1,
+                      void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream);
+int dd_mlp_train_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, int products,
+                     int splits, float* y, float* h, float* d, void* workspace, size_t workspace_bytes, void* stream);
+size_t dd_mlp_train_bwd_workspace_bytes(int M, int C, int splits);
+int dd_mlp_train_bwd(const float* g, const float* d, const void* pack_bwd2, const void* pack_bwd1_fused, int M, int C, int products, int splits, float* dx,
+                     float* gpre, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Weight AND bias gradient of those Linears, and of XCA's qkv / proj (reference networks/depth_encoder.py:200-203, :58-60), in one pass over
  * their operands (csrc/dd_linear_wgrad.hip): g_weight (cout,cin) = g_out^T . x and g_bias (cout) = the column sums of g_out, from the dense
  * row-major fp32 matrices g_out (M,cout) and x (M,cin) (any float alignment: the kernel loads dwords), each read ONCE; the rows are the
