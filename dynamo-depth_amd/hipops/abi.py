@@ -11,6 +11,7 @@ DD_ABI_VERSION = 2
 DD_MODE_RIGID, DD_MODE_FLOW, DD_MODE_FLOW_MASK = 0, 1, 2
 DD_PARTIAL_STRIDE = 40
 DD_SUMS_STRIDE = 8
+DD_OBJECTS_ROW = 22         # 32-bit words per row of dd_objects' table
 
 _fp = C.c_void_p        # device (or, for the host-math test library, host) float*
 
@@ -180,6 +181,9 @@ def declare(lib):
         "dd_export_plane_u8": (i, [v, i, i, i, i, i, v, v]),
         "dd_export_cloud_workspace_bytes": (z, [i, i, i, i]),
         "dd_export_cloud": (i, [v, v, v, v, v, v, i, i, i, i, i, f, f, f, f, f, f, f, f, f, i, v, v, v, z, v]),
+        "dd_objects_workspace_bytes": (z, [i, i, i, i]),
+        "dd_objects": (i, [v, v, v, v, v, v, v, i, i, i, f, f, f, f, f, f, f, i, i, i, v, v, v, v, z, v]),
+        "dd_export_labels_u16": (i, [v, i, i, i, i, i, v, v]),
         "dd_bn_act_fwd": (i, [v, v, C.c_longlong, i, v, v, f, f, v, v, v, v, i, v, v, z, v]),
         "dd_bn_act_bwd": (i, [v, v, v, C.c_longlong, i, v, v, v, v, i, v, v, v, v, v, z, v]),
         "dd_bn_workspace_bytes": (z, [i]),
@@ -278,7 +282,7 @@ EXPORTED = (
     "dd_ssim", "dd_ssim_bwd", "dd_disp_to_depth", "dd_pose_matrix", "dd_pose_matrix_bwd",
     "dd_channel_sum_nhwc", "dd_channel_sum_workspace_bytes", "dd_reflect_pad1_nhwc", "dd_reflect_pad1_nhwc_bwd",
     "dd_dwconv3x3_nhwc", "dd_dwconv3x3_nhwc_bwd_data", "dd_dwconv3x3_nhwc_bwd_weight", "dd_dwconv3x3_workspace_bytes", "dd_conv3x3_cout1_bwd_data",
-    "dd_prepare_frames", "dd_prepare_frames_workspace_bytes", "dd_pyramid_down2", "dd_pack_rgb", "dd_depth_metrics", "dd_depth_metrics_workspace_bytes", "dd_depth_metrics_masked", "dd_depth_metrics_masked_workspace_bytes", "dd_depth_metrics_accumulate", "dd_odom_snippet_count", "dd_odom_snippets", "dd_motion_pr", "dd_fill_contours", "dd_lidar_depth_points", "dd_lidar_depth_points_workspace_bytes", "dd_vis_frame", "dd_vis_flow_tiles", "dd_export_depth", "dd_export_plane_u8", "dd_export_cloud_workspace_bytes", "dd_export_cloud", "dd_bn_act_fwd", "dd_bn_act_bwd", "dd_bn_workspace_bytes",
+    "dd_prepare_frames", "dd_prepare_frames_workspace_bytes", "dd_pyramid_down2", "dd_pack_rgb", "dd_depth_metrics", "dd_depth_metrics_workspace_bytes", "dd_depth_metrics_masked", "dd_depth_metrics_masked_workspace_bytes", "dd_depth_metrics_accumulate", "dd_odom_snippet_count", "dd_odom_snippets", "dd_motion_pr", "dd_fill_contours", "dd_lidar_depth_points", "dd_lidar_depth_points_workspace_bytes", "dd_vis_frame", "dd_vis_flow_tiles", "dd_export_depth", "dd_export_plane_u8", "dd_export_cloud_workspace_bytes", "dd_export_cloud", "dd_objects_workspace_bytes", "dd_objects", "dd_export_labels_u16", "dd_bn_act_fwd", "dd_bn_act_bwd", "dd_bn_workspace_bytes",
     "dd_bn_act_fwd_t", "dd_bn_act_bwd_t", "dd_channel_sum_nhwc_t", "dd_reflect_pad1_nhwc_t", "dd_reflect_pad1_nhwc_bwd_t", "dd_up_cat_pad_t", "dd_up_cat_pad_bwd_t",
     "dd_layer_norm_fwd", "dd_layer_norm_bwd", "dd_layer_norm_workspace_bytes", "dd_layer_scale_bwd", "dd_layer_scale_workspace_bytes",
     "dd_jpeg_workspace_bytes", "dd_jpeg_decode", "dd_resize_workspace_bytes", "dd_resize_bicubic", "dd_layer_norm_fwd_t", "dd_layer_norm_bwd_t", "dd_layer_scale_bwd_t", "dd_layer_scale_fwd_t", "dd_dwconv3x3_nhwc_t", "dd_dwconv3x3_nhwc_bwd_data_t",

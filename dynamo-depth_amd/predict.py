@@ -1,8 +1,9 @@
 """Depth for a folder of frames, at the frames' own resolution:
 
     python predict.py <frames dir> -l <checkpoint folder> [--depth_model ...] [--height H --width W] [-b B] [--out <dir>]
-                      [--save depth16 npy color cloud] [--depth_scale 256] [--post_process] [--motion] [--scene]
+                      [--save depth16 npy color cloud objects] [--depth_scale 256] [--post_process] [--motion] [--scene]
                       [--intrinsics fx fy cx cy] [--cloud_stride 1] [--cloud_max_range R] [--cloud_edge 0.05] [--cloud_motion_thresh 0.5]
+                      [--object_motion_thresh 0.5] [--object_connectivity 8] [--object_min_pixels 16] [--object_max 256]
                       [--write_threads 8]
 
 The counterpart of the reference's quick demo on a few frames (its README's first offer; the demo notebook goes through
@@ -14,6 +15,8 @@ Per frame, named by the source file's stem:
     <out>/depth_npy/<stem>.npy    float32 depth                                                                  (--save npy)
     <out>/color/<stem>.png        the disparity through matplotlib's plasma map                                  (--save color)
     <out>/cloud/<stem>.ply        the frame as a coloured point cloud in its own camera coordinates (binary PLY)   (--save cloud)
+    <out>/objects/<stem>.png      16-bit label image of the moving objects at the source size, 0 = none       (--motion --save objects)
+    <out>/objects/<stem>.json     the frame's objects: id, pixels, box, centroid, motion, speed, confidence, z_min, z_max
     <out>/predict.json            min_depth, max_depth, depth_scale, the network resolution; depth is up to scale
 depth = 1 / bilinear(disp_to_depth(disp)) at the source size: the depth metrics' definition of a prediction (tools.py:42, 291-298),
 written by one kernel per batch (hipops.export, csrc/dd_export.hip); only the bytes that go to disk cross to the host.
@@ -26,6 +29,11 @@ writes the rest with the colours of the network-resolution frame: hipops.cloud, 
 --scene (with --motion, frames of one size) writes <out>/scene.ply: the points of every interior frame that the motion mask calls
 static (mask < --cloud_motion_thresh), moved by the chained poses into the coordinates of the first interior frame -- the static
 scene of the drive, the moving objects removed by the network's own mask.  Depth, and with it every cloud, is up to scale.
+--save objects (with --motion) describes what --scene removes: the connected components (--object_connectivity) of the motion mask at
+--object_motion_thresh and above, at the network's resolution, those of at least --object_min_pixels pixels numbered in row-major
+order of their first pixel, at most --object_max per frame.  Per object its size, its box in source pixels, the mean of its points in
+the frame's camera coordinates (centroid), its own mean 3-D motion to the neighbouring frame with the ego-motion removed (motion,
+speed), its mean mask value (confidence) and its depth range: hipops.objects, csrc/dd_objects.hip, labelled and reduced on the device.
 """
 import contextlib
 import json
@@ -50,6 +58,7 @@ from Trainer import Trainer  # noqa: E402
 
 MAX_THREADS = 16
 CLOUD = "cloud"         # --save cloud: not an output of export_depth
+OBJECTS = "objects"     # --save objects: neither
 SAVE = {"depth16": ("depth16", "depth", ".png"), "npy": ("depth", "depth_npy", ".npy"), "color": ("rgb", "color", ".png")}   # --save name -> (export output, folder, extension)
 SCALE_NOTE = "depth is up to scale: a self-supervised monocular network predicts it up to one unknown factor per model"
 
@@ -59,7 +68,7 @@ def parse(argv=None):
     p = options.p
     p.add_argument("frames_dir", type=str, help="a directory of .jpg / .jpeg / .png frames")
     p.add_argument("--out", type=str, default=None, help="output directory (default: <eval_dir>/predict/<frames dir's name>)")
-    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE) + [CLOUD], help="what to write per frame")
+    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE) + [CLOUD, OBJECTS], help="what to write per frame")
     p.add_argument("--depth_scale", type=float, default=256.0, help="the 16-bit image holds depth * depth_scale")
     p.add_argument("--post_process", action="store_true", help="fuse the disparities of the image and of its mirror image")
     p.add_argument("--motion", action="store_true", help="triplets of frames: also the motion mask and the pose of every interior frame")
@@ -70,8 +79,16 @@ def parse(argv=None):
     p.add_argument("--cloud_max_range", type=float, default=None, help="clouds drop points beyond this depth (default: max_depth)")
     p.add_argument("--cloud_edge", type=float, default=0.05, help="clouds drop pixels whose disparity taps differ by more than this fraction (0: keep them)")
     p.add_argument("--cloud_motion_thresh", type=float, default=0.5, help="--scene keeps the pixels whose motion mask is below this")
+    p.add_argument("--object_motion_thresh", type=float, default=0.5, help="--save objects: a pixel is foreground where its motion mask is at or above this")
+    p.add_argument("--object_connectivity", type=int, default=8, choices=[4, 8], help="--save objects: the neighbourhood that connects foreground pixels")
+    p.add_argument("--object_min_pixels", type=int, default=16, help="--save objects: smaller components (network pixels) are not objects")
+    p.add_argument("--object_max", type=int, default=256, help="--save objects: at most this many objects per frame (up to 65535)")
     opt = options.parse(args=argv)
     opt.print_opt = False
+    if OBJECTS in opt.save and not opt.motion:
+        p.error("--save objects needs --motion: the objects are the components of the motion mask, their motion comes from the motion networks")
+    if opt.object_min_pixels < 1 or not 1 <= opt.object_max <= 65535:
+        p.error("--object_min_pixels is at least 1 and --object_max between 1 and 65535")
     if opt.scene and not opt.motion:
         p.error("--scene needs --motion: the static scene is built from the motion masks and the poses of the interior frames")
     if opt.cloud_stride < 1:
@@ -108,10 +125,11 @@ def folder_dataset(opt, trainer, frames_dir, indices=None, intrinsics=None):
                          num_scales=len(opt.scales), is_train=False, path=True, intrinsics=intrinsics, **kwargs)
 
 
-def predict_batch(opt, trainer, inputs, post_process=False, motion=False, cloud=False):
+def predict_batch(opt, trainer, inputs, post_process=False, motion=False, cloud=False, objects=False):
     """Uploads the batch and runs the networks: {"disp": (B,1,h,w)} on the device, with post_process "disp_flipped" (the disparity of the
     mirrored image, not mirrored back), with motion "motion_mask" (B,1,h,w) and "cam_T_cam" (B,4,4) for frame 0 -> frame_ids[1], with
-    cloud "color" (B,3,h,w), the network-resolution frame."""
+    cloud "color" (B,3,h,w), the network-resolution frame, with objects (and motion) "complete_flow" (B,3,h,w) for frame_ids[1] and
+    "ts" (B,), that gap's time step where the dataset gives one, else 1."""
     with torch.no_grad():
         trainer.process_inputs(inputs)
         outputs = trainer.model(inputs)
@@ -124,6 +142,11 @@ def predict_batch(opt, trainer, inputs, post_process=False, motion=False, cloud=
             f = opt.frame_ids[1]
             res["motion_mask"] = outputs[("motion_mask", f, 0)]
             res["cam_T_cam"] = transformation_from_parameters(outputs[("axisangle", 0, f)], outputs[("translation", 0, f)], invert=True)
+        if motion and objects:
+            res["complete_flow"] = outputs[("complete_flow", f, 0)]
+            B = res["disp"].shape[0]
+            ts = inputs.get(("ts", f))
+            res["ts"] = torch.ones(B, device=res["disp"].device) if ts is None else torch.as_tensor(ts, dtype=torch.float32, device=res["disp"].device).reshape(B)
         if cloud:
             res["color"] = inputs[("color", 0, 0)]
     return res
@@ -155,6 +178,27 @@ def cloud_intrinsics(K, H, W):
     return (float(K[0, 0]) * W, float(K[1, 1]) * H, float(K[0, 2]) * W, float(K[1, 2]) * H)
 
 
+def object_parameters(opt):
+    """The objects' parameters from the options: what predict.json records."""
+    return {"motion_thresh": float(getattr(opt, "object_motion_thresh", 0.5)), "connectivity": int(getattr(opt, "object_connectivity", 8)),
+            "min_pixels": int(getattr(opt, "object_min_pixels", 16)), "max_objects": int(getattr(opt, "object_max", 256))}
+
+
+def export_objects(opt, res, H, W, intrinsics, params):
+    """The batch's objects on the device: (label images (B,H,W) uint16, table, counts).  `intrinsics`: in pixels of the network's frame."""
+    from hipops.objects import find_objects, labels_u16
+    labels, table, counts = find_objects(res["motion_mask"], res["disp"], res["complete_flow"].float(), res["ts"], res["cam_T_cam"].float(), intrinsics,
+                                         disp_flipped=res.get("disp_flipped"), min_depth=opt.min_depth, max_depth=opt.max_depth, thresh=params["motion_thresh"],
+                                         connectivity=params["connectivity"], min_pixels=params["min_pixels"], max_objects=params["max_objects"])
+    return labels_u16(labels, H, W), table, counts
+
+
+def _write_json(path, value):
+    with open(path, "w") as fh:
+        json.dump(value, fh, indent=1)
+    return path
+
+
 def export_clouds(opt, res, H, W, intrinsics, params, pose=None, static=False):
     """The batch's clouds as (records, offsets) on the device; `static`: the motion filter on (the scene), else never (a snapshot)."""
     from hipops.cloud import export_cloud
@@ -178,13 +222,16 @@ def _write(path, array):
 
 
 def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_scale=256.0, post_process=False, motion=False, intrinsics=None,
-                   write_threads=8, scene=False, cloud=None):
+                   write_threads=8, scene=False, cloud=None, objects=None):
     """Every frame of `frames_dir` (with motion: every interior frame) -> the files described above; returns the written paths.
     The main thread launches and makes one copy to the host per batch and requested output; a thread pool encodes and writes.
-    `cloud`: cloud_parameters(opt), for --save cloud and `scene`."""
+    `cloud`: cloud_parameters(opt), for --save cloud and `scene`; `objects`: object_parameters(opt), for --save objects."""
     from hipops.cloud import RECORD, ScenePly, write_ply
     save = tuple(dict.fromkeys(save))
-    want_cloud, save = CLOUD in save, tuple(name for name in save if name != CLOUD)
+    want_cloud, want_objects, save = CLOUD in save, OBJECTS in save, tuple(name for name in save if name not in (CLOUD, OBJECTS))
+    if want_objects and not motion:
+        raise ValueError("the objects need the motion networks (--motion)")
+    object_params = dict(objects) if objects is not None else object_parameters(opt)
     if scene and not motion:
         raise ValueError("the scene cloud needs the motion networks (--motion)")
     params = dict(cloud) if cloud is not None else cloud_parameters(opt)
@@ -198,11 +245,11 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
         by_size.setdefault(whole.get_gt_dim(None, i, None), []).append(i)
     if scene and len(by_size) != 1:
         raise ValueError("--scene needs frames of one size, {} holds {}".format(frames_dir, sorted(by_size)))
-    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else []) + ([CLOUD] if want_cloud else [])
+    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else []) + ([CLOUD] if want_cloud else []) + ([OBJECTS] if want_objects else [])
     ext = {SAVE[name][1]: SAVE[name][2] for name in save}
     for folder in folders:
         os.makedirs(osp.join(out_dir, folder), exist_ok=True)
-    pending, poses, counts, scene_counts, used_intrinsics = [], {}, {}, {}, {}
+    pending, poses, counts, scene_counts, used_intrinsics, object_counts = [], {}, {}, {}, {}, {}
     scene_file, chain = (ScenePly(osp.join(out_dir, "scene.ply")) if scene else None), None
     with ThreadPoolExecutor(max_workers=min(max(int(write_threads), 1), MAX_THREADS)) as pool, (scene_file or contextlib.nullcontext()):
         for (H, W), idx in sorted(by_size.items()):
@@ -211,11 +258,12 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                                 collate_fn=dataset.collate, **trainer._worker_start())
             for inputs in loader:
                 stems = list(inputs["paths"])
+                extra = dict(objects=True) if want_objects else {}           # only then: the call is what it was without
                 if want_cloud or scene:
-                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion, cloud=True)
+                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion, cloud=True, **extra)
                     camera = used_intrinsics.setdefault("{}x{}".format(H, W), cloud_intrinsics(dataset.K, H, W))
                 else:
-                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion)
+                    res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion, **extra)
                 files = export_batch(opt, res, H, W, save, depth_scale)
                 clouds = export_clouds(opt, res, H, W, camera, params) if want_cloud else None
                 pose = res["cam_T_cam"].reshape(-1, 16).cpu().numpy() if motion else None
@@ -231,6 +279,16 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                     for b, stem in enumerate(stems):
                         counts[stem] = int(off[b + 1] - off[b])
                         pending.append(pool.submit(write_ply, osp.join(out_dir, CLOUD, stem + ".ply"), data[off[b] * RECORD:off[b + 1] * RECORD]))
+                if want_objects:
+                    from hipops.objects import unpack_table
+                    h, w = res["disp"].shape[-2:]
+                    images, table, found = export_objects(opt, res, H, W, cloud_intrinsics(dataset.K, h, w), object_params)
+                    files[OBJECTS] = images                 # the label images go to the host with the other images below
+                    packed = torch.cat([table.reshape(len(stems), -1), found], dim=1).cpu().numpy()      # the batch's one copy of the tables
+                    frames = unpack_table(packed[:, :-3].reshape(tuple(table.shape)), packed[:, -3:], size=(h, w, H, W))
+                    for stem, frame in zip(stems, frames):
+                        object_counts[stem] = {"kept": len(frame["objects"]), "found": frame["found"], "truncated": frame["truncated"]}
+                        pending.append(pool.submit(_write_json, osp.join(out_dir, OBJECTS, stem + ".json"), frame))
                 for folder, tensor in files.items():
                     host = tensor.cpu().numpy()             # the batch's one copy of this output
                     for b, stem in enumerate(stems):
@@ -260,6 +318,11 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
         if scene:
             meta["cloud"]["scene_points"] = {stem: scene_counts[stem] for stem in order}
             meta["cloud"]["scene_total"] = int(sum(scene_counts.values()))
+    if want_objects:
+        from hipops.objects import MOTION_NOTE
+        meta["objects"] = dict(object_params, note=SCALE_NOTE, motion_note=MOTION_NOTE,
+                               convention="x right, y down, z forward; pixel centres at integer coordinates; boxes in source pixels, inclusive",
+                               frames={whole.stem(i): object_counts[whole.stem(i)] for i in indices})
     with open(path, "w") as fh:
         json.dump(meta, fh, indent=2)
     written.append(path)
@@ -270,7 +333,7 @@ def main(argv=None):
     opt = parse(argv)
     trainer = build_trainer(opt)
     written = predict_folder(opt, trainer, opt.frames_dir, opt.out, save=opt.save, depth_scale=opt.depth_scale, post_process=opt.post_process,
-                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads, scene=opt.scene, cloud=cloud_parameters(opt))
+                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads, scene=opt.scene, cloud=cloud_parameters(opt), objects=object_parameters(opt))
     print("{} files written to `{}`".format(len(written), opt.out))
     return written
 

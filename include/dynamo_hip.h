@@ -828,6 +828,41 @@ int dd_export_cloud(const float* disp, const float* disp_flipped, const float* l
                     float max_depth, float max_range, float edge, float motion_thresh, int stride, void* records, long long* offsets,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Moving objects as labelled instances (predict.py --save objects; csrc/dd_objects.hip): the connected components of the
+ * thresholded motion mask and one table row per object.  hipops/objects.py objects_host is the definition in numpy.
+ * All maps at the network's resolution: motion_mask (B,h,w), disp, disp_flipped, l_mask as dd_export_depth, complete_flow (B,3,h,w),
+ * ts (B), pose (B,3,4) row-major [R | t] of the transform from frame 0 to the neighbouring frame.  fx, fy, cx, cy: in pixels of the
+ * h x w image; 1/fx and 1/fy are evaluated in double and rounded to fp32 once.  lo, span: s = lo + span * d, as dd_disp_to_depth makes them.
+ * Foreground: motion_mask >= thresh (false for NaN).  A component is a maximal set of foreground pixels of one image connected through
+ * 4- or 8-neighbourhoods (connectivity); its anchor is its smallest index y*w + x.  Components of at least min_pixels pixels are the
+ * image's objects, numbered 1, 2, ... by increasing anchor; only the first max_objects of them are kept.
+ * labels (B,h,w) int32: the number of the pixel's kept object, else 0.
+ * counts (B,3) int32: the objects kept, the objects found, 1 where found > max_objects.
+ * table (B, max_objects, DD_OBJECTS_ROW 32-bit words), 8-byte aligned; the row of object n of image b is row (b, n-1):
+ *   word 0 pixels; 1 x0, 2 y0, 3 x1, 4 y1: the inclusive box; 5 anchor; 6 z_min, 7 z_max as fp32: fminf / fmaxf of z over the
+ *   object's pixels with 0 < z < inf, +inf and 0 where it has none; words 8..21 seven doubles: the sums over the object's pixels of
+ *   p[3], r[3] and motion_mask, each term the fp32 value below widened, in no fixed order (fp64 atomics).  Rows at and past the
+ *   image's kept count are all zero.
+ * Per pixel (y, x) of image b, fp32 and unfused: d the (fused) disparity, s = lo + span*d, z = 1/s, p = (xc*z, yc*z, z) with
+ *   xc = ((float)x - cx)/fx, yc = ((float)y - cy)/fy;  q_k = ((R[k,0] p0 + R[k,1] p1) + R[k,2] p2) + t[k];  r = complete_flow * ts[b] - (q - p):
+ *   the object's own motion between the two frames in frame 0's camera coordinates.  A pixel whose z is NaN, infinite or not
+ *   positive still belongs to its object and enters the sums; only that object's row can become NaN.
+ * workspace: dd_objects_workspace_bytes(B, h, w, max_objects), 8-byte aligned; every word the call reads it has written before.
+ * Five launches (tile, merge, flatten, number, reduce); no workgroup waits for another.
+ * dd_export_labels_u16: out (B,H,W) = min(labels[b, min(h-1, (2Y+1)*h / (2H)), min(w-1, (2X+1)*w / (2W))], 65535) in integer
+ * arithmetic: the label image at the source size, nearest neighbour.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer other than disp_flipped and l_mask, l_mask without disp_flipped or the
+ * reverse, B, h, w (H, W) below 1, B*h*w, H*W or B*max_objects above 2^31-1, connectivity other than 4 and 8, min_pixels below 1,
+ * max_objects outside 1..65535, fx or fy zero or not finite, a float, labels or counts pointer that is not 4-byte aligned, table or
+ * workspace not 8-byte aligned, out not 2-byte aligned, a workspace that is too small (the query returns 0 for sizes that are refused). */
+#define DD_OBJECTS_ROW 22
+size_t dd_objects_workspace_bytes(int B, int h, int w, int max_objects);
+int dd_objects(const float* motion_mask, const float* disp, const float* disp_flipped, const float* l_mask, const float* complete_flow,
+               const float* ts, const float* pose, int B, int h, int w, float fx, float fy, float cx, float cy, float lo, float span, float thresh,
+               int connectivity, int min_pixels, int max_objects, int* labels, void* table, int* counts, void* workspace,
+               size_t workspace_bytes, void* stream);
+int dd_export_labels_u16(const int* labels, int B, int h, int w, int H, int W, uint16_t* out, void* stream);
+
 const char* dd_error_string(int code);
 int dd_abi_version(void);
 
