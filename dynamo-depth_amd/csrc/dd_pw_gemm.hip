@@ -284,18 +284,41 @@ static int dispatch(const float* x, const void* pack, const float* bias, int M, 
 // the order fused_k() gives, and dd_mlp_pack lays W2 out in that order) -- no transposition, no LDS round trip for activations.  The
 // weight fragments of a hidden block (W1: C/16 x 3, W2: C/32 x 2 x 3 KB) go through LDS, shared by the four waves, prefetched into
 // registers one block ahead.  HBM traffic: x once, out once (35 MB at stage 1 against ~600 for two GEMMs and an element-wise pass).
-template <int C>
+// NP: the partial products kept (6 / 3 / 1, the last NP of cm::kPieceA/B as in mlp_fwd224_kernel).
+//
+// MODE (the training pass of stages 1 and 2): the loop of mlp_fwd224_kernel's modes at the narrow widths.
+//   MLP_TRAIN  besides the output, h = GELU(pre) and d = GELU'(pre) (M, 6C) go to memory straight from the accumulator: registers
+//              4 q .. 4 q + 3 of a lane are sixteen contiguous bytes of its pixel's row, lanes l and l + 32 complete 32, the four q of a
+//              hidden block a 128-byte line.  The pre-activation is never written; the output's arithmetic is MLP_FWD's, bit for bit.
+//   MLP_DGRAD  dx = ((g . W2) * d) . W1: x = g, pack1 = W2^T as first operand, pack2 = W1^T in fused-k order, no bias, no GELU: the
+//              accumulator times the d tile is stored as gpre (dd_linear_wgrad's operand) and is the second GEMM's A operand.
+// Both keep two workgroups per CU, which at C = 128 (254 VGPRs as MLP_FWD) leaves no register for anything new, so they give up the
+// weight prefetch in registers (48 at C = 128): the fragments go global -> LDS directly (global_load_lds_dwordx4), W1's and W2's parts of
+// the buffer refilled in turn, each while the other one is being read -- two barriers per hidden block as before.  The d tile (4 KB per
+// wave and hidden block, accumulator layout) takes the same road into a buffer of the wave's own, refilled once the wave has read it.
+// LDS per workgroup: 25.5 KB (+16 KB d tiles) at C = 64, 51 KB (+16) at C = 128: two workgroups fit the CU's 160 KB in every mode.
+// Rows at or beyond M are never stored (their x and d rows are clamped).
+constexpr int MLP_FWD = 0, MLP_TRAIN = 1, MLP_DGRAD = 2;
+constexpr int MLP_DTILE = 4096;                                 // one wave's d tile of a hidden block: 32 pixels x 32 hidden units
+
+template <int C, int NP, int MODE>
 __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict__ x, const uint4* __restrict__ pack1, const uint4* __restrict__ pack2,
-                                                         const float* __restrict__ b1, const float* __restrict__ b2, int M, float* __restrict__ y) {
+                                                         const float* __restrict__ b1, const float* __restrict__ b2, int M, float* __restrict__ y,
+                                                         const float* __restrict__ aux_in, float* __restrict__ out_a, float* __restrict__ out_b) {
   constexpr int KS1 = C / 16, NB2 = C / 32, HID = 6 * C, NHB = HID / 32;
   constexpr int NF1 = KS1 * 3, NF2 = NB2 * 6, NF = NF1 + NF2;      // fragments per hidden block
-  constexpr int BR = (NF + 3) / 4;
-  extern __shared__ __align__(16) unsigned char smem[];            // [NF fragments] | b1 (HID floats)
+  constexpr int BR = MODE == MLP_FWD ? (NF + 3) / 4 : 1;
+  static_assert(NF1 % 4 == 0 && NF2 % 4 == 0, "every wave moves the same number of fragments");
+  extern __shared__ __align__(16) unsigned char smem[];            // [NF fragments] | b1 (HID floats) | MLP_DGRAD: a d tile per wave
   float* const s_b1 = reinterpret_cast<float*>(smem + NF * FRAG);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), hh = lane >> 5;
   const int row0 = (int)blockIdx.x * 128 + wave * 32;
+  // this lane's pixel in the (M, 6C) tensors: element offset of its hidden unit 4 hh (the host keeps M * 6C * 4 below 2^32)
+  const bool row_ok = row0 + (lane & 31) < M;
+  const unsigned aoff = (unsigned)min(row0 + (lane & 31), M - 1) * (unsigned)HID + 4u * hh;
 
-  for (int i = tid; i < HID; i += 256) s_b1[i] = b1[i];
+  if (MODE != MLP_DGRAD)
+    for (int i = tid; i < HID; i += 256) s_b1[i] = b1[i];
   // x fragments of this wave's 32 rows (B operand of the first GEMM): lane = pixel lane & 31, channels ks * 16 + hh * 8 .. + 7
   uint4 xf[KS1][3];
   {
@@ -344,14 +367,8 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict
   float bv[NB2];         // the second bias, fetched first (dd_store_tile.h)
 #pragma unroll
   for (int n = 0; n < NB2; ++n) bv[n] = tile_bias(b2, n * 32 + (lane & 31), C, pack2);
-  fetch(0);
-  for (int hb = 0; hb < NHB; ++hb) {
-    lds_barrier();                       // the previous block's fragment reads are done (first pass: b1 is in place after the next one)
-    store_w();
-    lds_barrier();
-    fetch(min(hb + 1, NHB - 1));
-    // first GEMM, transposed: h^T (32 hidden x 32 pixels) = W1 block . x^T
-    f16v acc1;
+  // first GEMM, transposed: h^T (32 hidden x 32 pixels) = W1 block . x^T
+  auto gemm1 = [&](f16v& acc1) __attribute__((always_inline)) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc1[r] = 0.f;
 #pragma unroll
@@ -360,37 +377,156 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) wf[pc] = *reinterpret_cast<const uint4*>(w_lane + (ks * 3 + pc) * FRAG);
 #pragma unroll
-      for (int t = 0; t < 6; ++t)
+      for (int t = 6 - NP; t < 6; ++t)
         acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, wf[cm::kPieceA[t]]), __builtin_bit_cast(bf8, xf[ks][cm::kPieceB[t]]), acc1, 0, 0, 0);
     }
-    // bias + GELU on the accumulator: register r holds hidden unit hb * 32 + (r & 3) + 8 (r >> 2) + 4 hh of pixel lane & 31
-    float hv[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float4 bq = *reinterpret_cast<const float4*>(s_b1 + hb * 32 + 8 * q + 4 * hh);
-      hv[4 * q + 0] = gelu_erf(acc1[4 * q + 0] + bq.x);
-      hv[4 * q + 1] = gelu_erf(acc1[4 * q + 1] + bq.y);
-      hv[4 * q + 2] = gelu_erf(acc1[4 * q + 2] + bq.z);
-      hv[4 * q + 3] = gelu_erf(acc1[4 * q + 3] + bq.w);
+  };
+  // what stands between the two GEMMs, on the accumulator: register r holds hidden unit hb * 32 + (r & 3) + 8 (r >> 2) + 4 hh of pixel
+  // lane & 31.  MLP_FWD: bias + GELU.  MLP_TRAIN: the same (gelu_erf's arithmetic) and GELU' (gelu_pair_kernel's), both stored a quad at
+  // a time.  MLP_DGRAD: times the d tile, stored as gpre.
+  auto store_quad = [&](float* __restrict__ out, int hb, int q, const float* v) __attribute__((always_inline)) {
+    if (row_ok) *reinterpret_cast<float4*>(out + aoff + hb * 32 + 8 * q) = make_float4(v[0], v[1], v[2], v[3]);
+  };
+  // quad q: registers 4 q .. 4 q + 3 -> hv (h, or gpre); MLP_TRAIN: GELU' -> dv and h's two factors -> fx, fy; nothing is stored here
+  auto act_quad = [&](const f16v& acc1, int hb, int q, float (&hv)[16], float* dv, float* fx, float* fy) __attribute__((always_inline)) {
+    if (MODE == MLP_DGRAD) {
+      const float4 dq = *reinterpret_cast<const float4*>(smem + NF * FRAG + HID * 4 + wave * MLP_DTILE + q * FRAG + lane * 16);
+      hv[4 * q + 0] = acc1[4 * q + 0] * dq.x;
+      hv[4 * q + 1] = acc1[4 * q + 1] * dq.y;
+      hv[4 * q + 2] = acc1[4 * q + 2] * dq.z;
+      hv[4 * q + 3] = acc1[4 * q + 3] * dq.w;
+      return;
     }
-    // second GEMM: out (32 pixels x C) += h (A operand, straight from the registers) . W2 block
+    const float4 bq = *reinterpret_cast<const float4*>(s_b1 + hb * 32 + 8 * q + 4 * hh);
+    const float bqv[4] = {bq.x, bq.y, bq.z, bq.w};
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      unsigned p[3][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) split2(hv[8 * j + 2 * q], hv[8 * j + 2 * q + 1], p[0][q], p[1][q], p[2][q]);
-      uint4 hf[3];
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc) hf[pc] = make_uint4(p[pc][0], p[pc][1], p[pc][2], p[pc][3]);
-#pragma unroll
-      for (int n = 0; n < NB2; ++n) {
-        uint4 wf[3];
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) wf[pc] = *reinterpret_cast<const uint4*>(w_lane + (NF1 + (n * 2 + j) * 3 + pc) * FRAG);
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-          acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, hf[cm::kPieceA[t]]), __builtin_bit_cast(bf8, wf[cm::kPieceB[t]]), acc2[n], 0, 0, 0);
+    for (int e = 0; e < 4; ++e) {
+      const float v = acc1[4 * q + e] + bqv[e];
+      if (MODE == MLP_TRAIN) {                       // gelu_erf's expression for h, gelu_pair_kernel's arithmetic for d
+        const float er = 1.f + erf_poly(v * 0.70710678118654752440f);
+        const float pdf = __expf(-0.5f * v * v) * 0.3989422804014327f;
+        fx[e] = v * 0.5f;
+        fy[e] = er;
+        hv[4 * q + e] = fx[e] * fy[e];
+        dv[e] = fmaf(v, pdf, 0.5f * er);
+      } else {
+        hv[4 * q + e] = gelu_erf(v);
       }
+    }
+  };
+  // second GEMM: out (32 pixels x C) += h (A operand, straight from the registers) . W2 block, in two steps of sixteen hidden units
+  auto split_h = [&](const float (&hv)[16], int j, uint4 (&hf)[3]) __attribute__((always_inline)) {
+    unsigned p[3][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) split2(hv[8 * j + 2 * q], hv[8 * j + 2 * q + 1], p[0][q], p[1][q], p[2][q]);
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) hf[pc] = make_uint4(p[pc][0], p[pc][1], p[pc][2], p[pc][3]);
+  };
+  auto gemm2_step = [&](int j, const uint4 (&hf)[3]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int n = 0; n < NB2; ++n) {
+      uint4 wf[3];
+#pragma unroll
+      for (int pc = 0; pc < 3; ++pc) wf[pc] = *reinterpret_cast<const uint4*>(w_lane + (NF1 + (n * 2 + j) * 3 + pc) * FRAG);
+#pragma unroll
+      for (int t = 6 - NP; t < 6; ++t)
+        acc2[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, hf[cm::kPieceA[t]]), __builtin_bit_cast(bf8, wf[cm::kPieceB[t]]), acc2[n], 0, 0, 0);
+    }
+  };
+  if (MODE == MLP_FWD) {
+    fetch(0);
+    for (int hb = 0; hb < NHB; ++hb) {
+      lds_barrier();                       // the previous block's fragment reads are done (first pass: b1 is in place after the next one)
+      store_w();
+      lds_barrier();
+      fetch(min(hb + 1, NHB - 1));
+      f16v acc1;
+      float hv[16];
+      gemm1(acc1);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) act_quad(acc1, hb, q, hv, nullptr, nullptr, nullptr);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        uint4 hf[3];
+        split_h(hv, j, hf);
+        gemm2_step(j, hf);
+      }
+    }
+  } else {
+    // `count` fragments of one operand's hidden block hb -> LDS from fragment `first` on, without passing registers (1 KB per
+    // wave-instruction, lane l at byte 16 l: the fragment's own order); wave w moves the fragments w, w + 4, ...  The compiler does not
+    // count these loads: wait_barrier() waits for them, and nothing reads a buffer between its dma() and the next wait_barrier().
+    const unsigned lds0 = (unsigned)reinterpret_cast<size_t>(smem);
+    auto dma = [&](const uint4* pack, int count, int first, int hb) __attribute__((always_inline)) {
+      const uint4* src = pack + (size_t)hb * (count * 64) + lane;
+#pragma unroll
+      for (int r = 0; r < count / 4; ++r) {
+        const int f = wave + 4 * r;
+        const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)((first + f) * FRAG));
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src + f * 64), "s"(dst) : "memory");
+      }
+    };
+    // MLP_DGRAD: this wave's d tile of hidden block hb in accumulator layout: instruction q moves, for every lane, the four hidden units
+    // 8 q + 4 hh .. + 3 of its pixel (the accumulator's registers 4 q .. 4 q + 3) to byte q * 1024 + 16 lane of the wave's buffer
+    auto dma_d = [&](int hb) __attribute__((always_inline)) {
+      const float* src = aux_in + aoff + hb * 32;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(NF * FRAG + HID * 4 + wave * MLP_DTILE + q * FRAG));
+        unsigned keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src + 8 * q), "s"(dst) : "memory");
+      }
+    };
+    // every load, store and LDS operation of this wave has completed (what it moved has landed), then the barrier
+    auto wait_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    dma(pack1, NF1, 0, 0);
+    if (MODE == MLP_DGRAD) dma_d(0);
+    for (int hb = 0; hb < NHB; ++hb) {
+      wait_barrier();                      // the first operand of block hb (and its d tile, and b1) is in place, every wave has left block hb - 1
+      dma(pack2, NF2, NF1, hb);            // lands under the first GEMM
+      f16v acc1;
+      float hv[16];
+      gemm1(acc1);
+      // Per half of the block: activation, split, stores.  MLP_TRAIN splits h = fx * fy with the first residual taken from the UNROUNDED
+      // product (one fma): that is what the compiler makes of gelu_erf + split2 in MLP_FWD (it contracts h's last product into
+      // a - bf16(a)), and here the conditional stores between product and split keep it from doing so -- y bit for bit needs the same
+      // arithmetic, so it is spelled out; tests/test_mlp_narrow_train_gpu.py holds the two together.
+      uint4 hf[2][3];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        float dv[8], fx[8], fy[8];
+        act_quad(acc1, hb, 2 * j, hv, dv, fx, fy);
+        act_quad(acc1, hb, 2 * j + 1, hv, dv + 4, fx + 4, fy + 4);
+        if (MODE == MLP_TRAIN) {
+          unsigned p[3][4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            p[0][q] = cm::pack_bf16(hv[8 * j + 2 * q], hv[8 * j + 2 * q + 1]);
+            const float ra = fmaf(fx[2 * q], fy[2 * q], -cm::lo_f(p[0][q])), rb = fmaf(fx[2 * q + 1], fy[2 * q + 1], -cm::hi_f(p[0][q]));
+            p[1][q] = cm::pack_bf16(ra, rb);
+            p[2][q] = cm::pack_bf16(ra - cm::lo_f(p[1][q]), rb - cm::hi_f(p[1][q]));
+          }
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc) hf[j][pc] = make_uint4(p[pc][0], p[pc][1], p[pc][2], p[pc][3]);
+        } else {
+          split_h(hv, j, hf[j]);
+        }
+#pragma unroll
+        for (int q = 2 * j; q < 2 * j + 2; ++q) {
+          store_quad(out_a, hb, q, hv + 4 * q);
+          if (MODE == MLP_TRAIN) store_quad(out_b, hb, q, dv + 4 * (q - 2 * j));
+        }
+      }
+      wait_barrier();                      // the second operand is in place, every wave has read the first one (and its own d tile)
+      if (hb + 1 < NHB) {                  // lands under the second GEMM
+        dma(pack1, NF1, 0, hb + 1);
+        if (MODE == MLP_DGRAD) dma_d(hb + 1);
+      }
+      gemm2_step(0, hf[0]);
+      gemm2_step(1, hf[1]);
     }
   }
   auto tail = [&](auto full) {
@@ -403,14 +539,26 @@ __global__ __launch_bounds__(256, 2) void mlp_fwd_kernel(const float* __restrict
   else tail(std::false_type{});
 }
 
-template <int C>
-static int launch_fused(const float* x, const void* pack1, const void* pack2, const float* b1, const float* b2, int M, float* y, hipStream_t stream) {
-  constexpr int lds = ((C / 16) * 3 + (C / 32) * 6) * FRAG + 6 * C * 4;
-  auto kern = mlp_fwd_kernel<C>;
+// MLP_FWD / MLP_TRAIN: y = the block's output (out_a = h, out_b = d for MLP_TRAIN).  MLP_DGRAD: x = g, aux_in = d, pack1 = W2^T, pack2 =
+// W1^T fused, b1 = b2 = nullptr, y = dx, out_a = gpre.
+template <int C, int NP, int MODE>
+static int launch_fused(const float* x, const void* pack1, const void* pack2, const float* b1, const float* b2, int M, float* y, hipStream_t stream,
+                        const float* aux_in = nullptr, float* out_a = nullptr, float* out_b = nullptr) {
+  constexpr int lds = ((C / 16) * 3 + (C / 32) * 6) * FRAG + 6 * C * 4 + (MODE == MLP_DGRAD ? 4 * MLP_DTILE : 0);
+  auto kern = mlp_fwd_kernel<C, NP, MODE>;
   static dd::LdsAttrOnce lds_attr;          // per instantiation and device (dd_attr.h)
   if (const int rc = lds_attr.ensure(reinterpret_cast<const void*>(kern), (int)(lds))) return rc;
-  hipLaunchKernelGGL(kern, dim3((M + 127) / 128), dim3(256), lds, stream, x, static_cast<const uint4*>(pack1), static_cast<const uint4*>(pack2), b1, b2, M, y);
+  hipLaunchKernelGGL(kern, dim3((M + 127) / 128), dim3(256), lds, stream, x, static_cast<const uint4*>(pack1), static_cast<const uint4*>(pack2), b1, b2, M, y,
+                     aux_in, out_a, out_b);
   return (int)hipGetLastError();
+}
+
+template <int C, int MODE>
+static int launch_fused_n(int products, const float* x, const void* pack1, const void* pack2, const float* b1, const float* b2, int M, float* y,
+                          hipStream_t stream, const float* aux_in, float* out_a, float* out_b) {
+  return products == 6 ? launch_fused<C, 6, MODE>(x, pack1, pack2, b1, b2, M, y, stream, aux_in, out_a, out_b)
+       : products == 3 ? launch_fused<C, 3, MODE>(x, pack1, pack2, b1, b2, M, y, stream, aux_in, out_a, out_b)
+                       : launch_fused<C, 1, MODE>(x, pack1, pack2, b1, b2, M, y, stream, aux_in, out_a, out_b);
 }
 
 // ---- the same block at C = 224 (LiteMono's stage 3: 5 760 / 11 520 rows, hidden 1344 = 42 blocks) -----------------------------------
@@ -444,8 +592,7 @@ static_assert(NF3 == NB3 * 6, "both operands of a hidden block have the same num
 // Stores count in vmcnt, in order, and wait_barrier() waits for all of them: the stores of h and gpre go out from the slices right BEHIND
 // the mid-block barrier (the values are held for the split anyway), those of d when a quad is complete (at 252 VGPRs there is no room to
 // hold them).
-constexpr int MLP_FWD = 0, MLP_TRAIN = 1, MLP_DGRAD = 2;
-constexpr int MLP3_DTILE = 4096;                                // one wave's d tile of a hidden block: 32 pixels x 32 hidden units
+constexpr int MLP3_DTILE = MLP_DTILE;
 
 template <int NP, int MODE>
 __global__ __launch_bounds__(256, 1) void mlp_fwd224_kernel(const float* __restrict__ x, const uint4* __restrict__ pack1, const uint4* __restrict__ pack2,
@@ -749,11 +896,14 @@ extern "C" int dd_mlp_pack(const float* w1, long long s1_n, long long s1_k, cons
   return (int)hipGetLastError();
 }
 
-// ---- the training pass of the stage-3 block (C = 224): forward that saves h and d, fused data gradient ------------------------------
-extern "C" int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
-                                 void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream) {
+// ---- the training pass of the block: forward that saves h and d, fused data gradient (C = 224: stage 3; C = 64 / 128: stages 1, 2) ----
+static bool mlp_narrow(int C) { return C == 64 || C == 128; }
+
+// the four operands of a training block in one launch; each entry point names the widths it takes
+static int mlp_train_pack(bool width_ok, const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
+                          void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream) {
   using namespace dd::pw;
-  if (!w1 || !w2 || C != C3 || hidden != 6 * C3 || !pack_fwd1 || !pack_fwd2_fused || !pack_bwd2 || !pack_bwd1_fused) return (int)hipErrorInvalidValue;
+  if (!w1 || !w2 || !width_ok || hidden != 6 * C || !pack_fwd1 || !pack_fwd2_fused || !pack_bwd2 || !pack_bwd1_fused) return (int)hipErrorInvalidValue;
   PackArgs a;
   a.count = 0;
   a.total = 0;
@@ -771,16 +921,28 @@ extern "C" int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k
   return (int)hipGetLastError();
 }
 
+extern "C" int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
+                                 void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream) {
+  return mlp_train_pack(C == dd::pw::C3, w1, s1_n, s1_k, w2, s2_n, s2_k, C, hidden, pack_fwd1, pack_fwd2_fused, pack_bwd2, pack_bwd1_fused, stream);
+}
+
+extern "C" int dd_mlp_train_pack_narrow(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
+                                        void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream) {
+  return mlp_train_pack(mlp_narrow(C), w1, s1_n, s1_k, w2, s2_n, s2_k, C, hidden, pack_fwd1, pack_fwd2_fused, pack_bwd2, pack_bwd1_fused, stream);
+}
+
 extern "C" size_t dd_mlp_train_bwd_workspace_bytes(int M, int C, int splits) {
   if (M < 1 || C != dd::pw::C3 || splits < 0 || splits > dd::pw::NHB3) return 0;
   const int S = splits ? splits : dd::pw::mlp224_splits(M);
   return S > 1 ? (size_t)S * M * C * sizeof(float) : 0;
 }
 
-// what both training entry points refuse: another width, rows whose (M, 1344) tensors pass 2^32 bytes (the kernel's 32-bit offsets),
-// more splits than hidden blocks, an unknown product count
+// what both training entry points refuse: another width, rows whose (M, 6C) tensors pass 2^32 bytes (the kernels' 32-bit offsets),
+// more splits than hidden blocks (C = 64 / 128: any split, the hidden range stays whole there), an unknown product count
 static bool mlp_train_shape_ok(int M, int C, int products, int splits) {
-  return C == dd::pw::C3 && M >= 1 && M <= (1 << 19) && splits >= 0 && splits <= dd::pw::NHB3 && (products == 6 || products == 3 || products == 1);
+  if (products != 6 && products != 3 && products != 1) return false;
+  if (mlp_narrow(C)) return M >= 1 && (long long)M * (6 * C) < (1ll << 30) && splits >= 0 && splits <= 1;
+  return C == dd::pw::C3 && M >= 1 && M <= (1 << 19) && splits >= 0 && splits <= dd::pw::NHB3;
 }
 
 static bool aligned16(std::initializer_list<const void*> ps) {
@@ -794,6 +956,8 @@ extern "C" int dd_mlp_train_fwd(const float* x, const void* pack_fwd1, const voi
   using namespace dd::pw;
   if (!x || !pack_fwd1 || !pack_fwd2_fused || !b1 || !b2 || !y || !h || !d || !mlp_train_shape_ok(M, C, products, splits)) return (int)hipErrorInvalidValue;
   if (!aligned16({x, y, h, d, b2, workspace, pack_fwd1, pack_fwd2_fused})) return (int)hipErrorInvalidValue;
+  if (C == 64) return launch_fused_n<64, MLP_TRAIN>(products, x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, static_cast<hipStream_t>(stream), nullptr, h, d);
+  if (C == 128) return launch_fused_n<128, MLP_TRAIN>(products, x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, static_cast<hipStream_t>(stream), nullptr, h, d);
   const int S = splits ? splits : mlp224_splits(M);
   if (S > 1 && (!workspace || workspace_bytes < dd_mlp_fwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -808,6 +972,8 @@ extern "C" int dd_mlp_train_bwd(const float* g, const float* d, const void* pack
   using namespace dd::pw;
   if (!g || !d || !pack_bwd2 || !pack_bwd1_fused || !dx || !gpre || !mlp_train_shape_ok(M, C, products, splits)) return (int)hipErrorInvalidValue;
   if (!aligned16({g, d, dx, gpre, workspace, pack_bwd2, pack_bwd1_fused})) return (int)hipErrorInvalidValue;
+  if (C == 64) return launch_fused_n<64, MLP_DGRAD>(products, g, pack_bwd2, pack_bwd1_fused, nullptr, nullptr, M, dx, static_cast<hipStream_t>(stream), d, gpre, nullptr);
+  if (C == 128) return launch_fused_n<128, MLP_DGRAD>(products, g, pack_bwd2, pack_bwd1_fused, nullptr, nullptr, M, dx, static_cast<hipStream_t>(stream), d, gpre, nullptr);
   const int S = splits ? splits : mlp224_splits(M);
   if (S > 1 && (!workspace || workspace_bytes < dd_mlp_train_bwd_workspace_bytes(M, C, S))) return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -849,8 +1015,8 @@ extern "C" int dd_mlp_fwd(const float* x, const void* pack_fwd1, const void* pac
   if (!x || !pack_fwd1 || !pack_fwd2_fused || !b1 || !b2 || !y || M < 1 || (reinterpret_cast<unsigned long long>(x) & 15ull)) return (int)hipErrorInvalidValue;
   hipStream_t s = static_cast<hipStream_t>(stream);
   switch (C) {
-    case 64: return dd::pw::launch_fused<64>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
-    case 128: return dd::pw::launch_fused<128>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
+    case 64: return dd::pw::launch_fused<64, 6, dd::pw::MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
+    case 128: return dd::pw::launch_fused<128, 6, dd::pw::MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, y, s);
     case 224: return dd::pw::launch_fused224<6, dd::pw::MLP_FWD>(x, pack_fwd1, pack_fwd2_fused, b1, b2, M, 1, y, nullptr, s);      // unsplit: dd_mlp_fwd_n fills the chip
     default: return (int)hipErrorInvalidValue;
   }

@@ -251,6 +251,7 @@ def declare(lib):
         "dd_pw_gemm": (i, [v, v, v, i, i, i, i, v, v]),
         "dd_gelu_pair": (i, [v, v, v, z, v]),
         "dd_mlp_train_pack": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v]),
+        "dd_mlp_train_pack_narrow": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v]),
         "dd_mlp_train_fwd": (i, [v, v, v, v, v, i, i, i, i, v, v, v, v, z, v]),
         "dd_mlp_train_bwd_workspace_bytes": (z, [i, i, i]),
         "dd_mlp_train_bwd": (i, [v, v, v, v, i, i, i, i, v, v, v, z, v]),
@@ -296,7 +297,7 @@ EXPORTED = (
     "dd_conv3x3_half_supported", "dd_conv3x3_half_pack_bytes", "dd_conv3x3_half_pack", "dd_conv3x3_half",
     "dd_conv3x3_half_wgrad_workspace_bytes", "dd_conv3x3_half_bwd_weight",
     "dd_pw_gemm_pack_bytes", "dd_mlp_pack", "dd_pw_gemm", "dd_gelu_pair", "dd_mlp_fwd_supported", "dd_mlp_fwd", "dd_mlp_fwd_splits", "dd_mlp_fwd_workspace_bytes", "dd_mlp_fwd_n",
-    "dd_mlp_train_pack", "dd_mlp_train_fwd", "dd_mlp_train_bwd_workspace_bytes", "dd_mlp_train_bwd",
+    "dd_mlp_train_pack", "dd_mlp_train_pack_narrow", "dd_mlp_train_fwd", "dd_mlp_train_bwd_workspace_bytes", "dd_mlp_train_bwd",
     "dd_linear_wgrad_supported", "dd_linear_wgrad_workspace_bytes", "dd_linear_wgrad", "dd_linear_wgrad_n",
     "dd_error_string", "dd_abi_version",
 )

@@ -1190,6 +1190,45 @@ def mlp_train_ok(y, block):
                 and getattr(block.act, "approximate", "none") == "none")
 
 
+def _mlp_train_forward(ctx, pack, calls, y, w1, b1, w2, b2):
+    """what MlpTrainFn and MlpTrainNarrowFn run forward: `pack` names the width's pack entry point, `calls` is the path's counter"""
+    lib = L.load()
+    B, H, W, Cc = y.shape
+    hid, M = w1.shape[0], B * H * W
+    nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)          # all four operands have hidden x C elements
+    packs = torch.empty(nb, dtype=torch.float32, device=y.device)      # fwd1 | fwd2 fused | bwd2 | bwd1 fused
+    p0, stream = packs.data_ptr(), L.current_stream()
+    L.check(getattr(lib, pack)(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, p0 + nb, p0 + 2 * nb,
+                               p0 + 3 * nb, stream), pack)
+    out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
+    h = torch.empty((M, hid), dtype=torch.float32, device=y.device)
+    d = torch.empty((M, hid), dtype=torch.float32, device=y.device)
+    nbytes = _ws_bytes("dd_mlp_fwd_workspace_bytes", M, Cc, 0)
+    ws = _ws(nbytes, y.device)
+    L.check(lib.dd_mlp_train_fwd(_p(y), p0, p0 + nb, _p(b1), _p(b2), M, Cc, mfma_products(), 0, _p(out), _p(h), _p(d), _p(ws), nbytes, stream),
+            "dd_mlp_train_fwd")
+    calls[0] += 1
+    ctx.save_for_backward(y, h, d, w1, w2, packs)
+    return out
+
+
+def _mlp_train_backward(ctx, g):
+    y, h, d, w1, w2, packs = ctx.saved_tensors
+    lib = L.load()
+    B, H, W, Cc = y.shape
+    hid, M = w1.shape[0], B * H * W
+    nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)
+    p0, stream = packs.data_ptr(), L.current_stream()
+    g = g.to(torch.float32).contiguous()
+    gy = torch.empty((B, H, W, Cc), dtype=torch.float32, device=g.device)
+    gpre = torch.empty((M, hid), dtype=torch.float32, device=g.device)
+    nbytes = _ws_bytes("dd_mlp_train_bwd_workspace_bytes", M, Cc, 0)
+    ws = _ws(nbytes, g.device)
+    L.check(lib.dd_mlp_train_bwd(_p(g), _p(d), p0 + 2 * nb, p0 + 3 * nb, M, Cc, mfma_products(), 0, _p(gy), _p(gpre), _p(ws), nbytes, stream),
+            "dd_mlp_train_bwd")
+    return (gy if ctx.needs_input_grad[0] else None,) + _mlp_param_grads(ctx.needs_input_grad, g, gpre, y, h, w1, w2, B, H, W, stream)
+
+
 class MlpTrainFn(torch.autograd.Function):
     """pwconv2(GELU(pwconv1(y))) of a stage-3 LiteMono block (C = 224) in a TRAINING pass (reference networks/depth_encoder.py:200-203,
     216-224,262-272), csrc/dd_pw_gemm.hip.  Forward: dd_mlp_train_pack (one launch, four operands), then dd_mlp_fwd_n's kernel, which also
@@ -1199,45 +1238,65 @@ class MlpTrainFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, y, w1, b1, w2, b2):
-        lib = L.load()
-        B, H, W, Cc = y.shape
-        hid, M = w1.shape[0], B * H * W
-        nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)          # all four operands have hidden x C elements
-        packs = torch.empty(nb, dtype=torch.float32, device=y.device)      # fwd1 | fwd2 fused | bwd2 | bwd1 fused
-        p0, stream = packs.data_ptr(), L.current_stream()
-        L.check(lib.dd_mlp_train_pack(_p(w1), w1.stride(0), w1.stride(1), _p(w2), w2.stride(0), w2.stride(1), Cc, hid, p0, p0 + nb, p0 + 2 * nb,
-                                      p0 + 3 * nb, stream), "dd_mlp_train_pack")
-        out = torch.empty((B, H, W, Cc), dtype=torch.float32, device=y.device)
-        h = torch.empty((M, hid), dtype=torch.float32, device=y.device)
-        d = torch.empty((M, hid), dtype=torch.float32, device=y.device)
-        nbytes = _ws_bytes("dd_mlp_fwd_workspace_bytes", M, Cc, 0)
-        ws = _ws(nbytes, y.device)
-        L.check(lib.dd_mlp_train_fwd(_p(y), p0, p0 + nb, _p(b1), _p(b2), M, Cc, mfma_products(), 0, _p(out), _p(h), _p(d), _p(ws), nbytes, stream),
-                "dd_mlp_train_fwd")
-        _MLP_TRAIN_CALLS[0] += 1
-        ctx.save_for_backward(y, h, d, w1, w2, packs)
-        return out
+        return _mlp_train_forward(ctx, "dd_mlp_train_pack", _MLP_TRAIN_CALLS, y, w1, b1, w2, b2)
 
     @staticmethod
     def backward(ctx, g):
-        y, h, d, w1, w2, packs = ctx.saved_tensors
-        lib = L.load()
-        B, H, W, Cc = y.shape
-        hid, M = w1.shape[0], B * H * W
-        nb = _ws_bytes("dd_pw_gemm_pack_bytes", hid, Cc)
-        p0, stream = packs.data_ptr(), L.current_stream()
-        g = g.to(torch.float32).contiguous()
-        gy = torch.empty((B, H, W, Cc), dtype=torch.float32, device=g.device)
-        gpre = torch.empty((M, hid), dtype=torch.float32, device=g.device)
-        nbytes = _ws_bytes("dd_mlp_train_bwd_workspace_bytes", M, Cc, 0)
-        ws = _ws(nbytes, g.device)
-        L.check(lib.dd_mlp_train_bwd(_p(g), _p(d), p0 + 2 * nb, p0 + 3 * nb, M, Cc, mfma_products(), 0, _p(gy), _p(gpre), _p(ws), nbytes, stream),
-                "dd_mlp_train_bwd")
-        return (gy if ctx.needs_input_grad[0] else None,) + _mlp_param_grads(ctx.needs_input_grad, g, gpre, y, h, w1, w2, B, H, W, stream)
+        return _mlp_train_backward(ctx, g)
 
 
 def mlp_train(y, block):
     return MlpTrainFn.apply(y, block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias)
+
+
+_MLP_TRAIN_NARROW_CALLS = [0]
+
+# rows from which the training pass of a stage-1 / stage-2 block (forward + backward with the weight gradients) is ahead of the library's,
+# by width: the per-shape table of profiles/mlp_narrow_train.txt.  A width without an entry stays with the library.
+_MLP_TRAIN_NARROW_MIN_ROWS = {64: 15360, 128: 23040}
+
+
+def mlp_train_narrow_calls():
+    """How many TRAINING block forwards MlpTrainNarrowFn has run through dd_mlp_train_fwd at C = 64 / 128 in this process."""
+    return _MLP_TRAIN_NARROW_CALLS[0]
+
+
+def mlp_train_narrow_ok(y, block):
+    """The training pass of this block takes MlpTrainNarrowFn: tape on, fp32, no autocast, C = 64 or 128 with the 6x expansion and the erf
+    GELU, contiguous (B,H,W,C), rows from the width's gate (_MLP_TRAIN_NARROW_MIN_ROWS; DD_MLP_TRAIN_NARROW_MIN_ROWS overrides it for both
+    widths).  DD_MLP_TRAIN_NARROW=0 or DD_STOCK_MLP=1 turn it off."""
+    if (not torch.is_grad_enabled() or os.environ.get("DD_MLP_TRAIN_NARROW", "1") != "1" or os.environ.get("DD_STOCK_MLP", "0") == "1"
+            or torch.is_autocast_enabled()):
+        return False
+    l1, l2 = block.pwconv1, block.pwconv2
+    Cc = l1.in_features
+    if not (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.is_contiguous() and Cc in (64, 128) and y.shape[-1] == Cc
+            and l1.weight.dtype == torch.float32 and l2.weight.dtype == torch.float32):
+        return False
+    min_rows = os.environ.get("DD_MLP_TRAIN_NARROW_MIN_ROWS")
+    gate = int(min_rows) if min_rows is not None else _MLP_TRAIN_NARROW_MIN_ROWS.get(Cc)
+    if gate is None or y.shape[0] * y.shape[1] * y.shape[2] < gate:
+        return False
+    return bool(l1.bias is not None and l2.bias is not None and l1.out_features == 6 * Cc and l2.in_features == l1.out_features
+                and l2.out_features == Cc and isinstance(block.act, torch.nn.GELU) and getattr(block.act, "approximate", "none") == "none")
+
+
+class MlpTrainNarrowFn(torch.autograd.Function):
+    """MlpTrainFn at the widths of stages 1 and 2 (C = 64 / 128): dd_mlp_train_pack_narrow, then dd_mlp_train_fwd / dd_mlp_train_bwd on
+    mlp_fwd_kernel's MLP_TRAIN / MLP_DGRAD forms (no hidden split, no fold), _mlp_param_grads as there.  Two library GEMMs and ATen's GELU
+    forward, two GEMMs and ATen's GELU backward become one kernel each way; everything is bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, y, w1, b1, w2, b2):
+        return _mlp_train_forward(ctx, "dd_mlp_train_pack_narrow", _MLP_TRAIN_NARROW_CALLS, y, w1, b1, w2, b2)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _mlp_train_backward(ctx, g)
+
+
+def mlp_train_narrow(y, block):
+    return MlpTrainNarrowFn.apply(y, block.pwconv1.weight, block.pwconv1.bias, block.pwconv2.weight, block.pwconv2.bias)
 
 
 BN_ACTS = {None: 0, "relu": 1, "gelu": 2}

@@ -223,8 +223,8 @@ def _mlp_residual(block, y, res):
     residual are one addcmul instead of three element-wise passes."""
     B, H, W, Cc = y.shape
     if y.is_cuda and os.environ.get("DD_STOCK_LINEAR_GRAD", "0") != "1":
-        from hipops.functions import (mlp, mlp_fused, mlp_fused_ok, mlp_ok, mlp_recompute, mlp_recompute_ok, mlp_train, mlp_train_ok,
-                                      pointwise_linear)
+        from hipops.functions import (mlp, mlp_fused, mlp_fused_ok, mlp_ok, mlp_recompute, mlp_recompute_ok, mlp_train, mlp_train_narrow,
+                                      mlp_train_narrow_ok, mlp_train_ok, pointwise_linear)
         y = y.contiguous()
         if mlp_fused_ok(y, block):
             y = mlp_fused(y, block)                            # forward-only pass: the whole block in one kernel, hidden tile on chip
@@ -234,6 +234,8 @@ def _mlp_residual(block, y, res):
             y = mlp_recompute(y, block)                        # training pass: the same kernel forward, the hidden tensor rebuilt in the backward
         elif mlp_ok(y, block):
             y = mlp(y, block)                                  # csrc/dd_pw_gemm.hip: both Linears on the bf16 matrix pipe (fp32 accuracy), GELU in the second one's prologue
+        elif mlp_train_narrow_ok(y, block):
+            y = mlp_train_narrow(y, block)                     # stages 1 and 2 with a tape: mlp_train's design at C = 64 / 128 (behind the two opt-ins)
         else:                                                  # weight + bias gradient: one pass of dd_linear_wgrad
             y = pointwise_linear(block.act(pointwise_linear(y, block.pwconv1)), block.pwconv2)
     else:

@@ -692,8 +692,12 @@ int dd_mlp_fwd_n(const float* x, const void* pack_fwd1, const void* pack_fwd2_fu
 int dd_pw_gemm(const float* x, const void* pack, const float* bias, int M, int K, int N, int gelu_in, float* y, void* stream);
 int dd_gelu_pair(const float* pre, float* g_inout, float* post, size_t n, void* stream);
 
-/* The TRAINING pass of the stage-3 block (reference networks/depth_encoder.py:200-203,216-224,262-272 at C = 224, hidden 1344: pwconv1 ->
- * GELU -> pwconv2 with a tape, and its data gradient) in dd_mlp_fwd_n's kernel (csrc/dd_pw_gemm.hip: mlp_fwd224_kernel, MLP_TRAIN / MLP_DGRAD).
+/* The TRAINING pass of the block (reference networks/depth_encoder.py:200-203,216-224,262-272: pwconv1 -> GELU -> pwconv2 with a tape, and
+ * its data gradient) in dd_mlp_fwd_n's kernels (csrc/dd_pw_gemm.hip: mlp_fwd224_kernel and mlp_fwd_kernel as MLP_TRAIN / MLP_DGRAD).  Written
+ * below for the stage-3 block (C = 224, hidden 1344); dd_mlp_train_fwd and dd_mlp_train_bwd also take the narrow widths of stages 1 and 2
+ * (C = 64 / 128, hidden 6C, operands from dd_mlp_train_pack_narrow -- dd_mlp_train_pack's arguments and layouts): there the hidden range
+ * stays whole (splits 0 or 1 only, anything else is refused; no workspace: dd_mlp_train_bwd_workspace_bytes is 0), y is dd_mlp_fwd's bit for
+ * bit at six products, and M * 6C must stay below 2^30.
  * dd_mlp_train_pack: ONE launch writes the four operands a training block needs, each dd_pw_gemm_pack_bytes(hidden, C) bytes, 16-byte
  * aligned: pack_fwd1 and pack_fwd2_fused as dd_mlp_pack writes them, pack_bwd2 = w2 transposed as a first operand (n = hidden, k = C) and
  * pack_bwd1_fused = w1 transposed by hidden block in the accumulator's contraction order (n = C, k = hidden).
@@ -703,12 +707,14 @@ int dd_gelu_pair(const float* pre, float* g_inout, float* post, size_t n, void* 
  * dd_mlp_train_bwd: dx (M,224) = ((g . w2) * d) . w1 in one kernel and gpre (M,1344) = (g . w2) * d, the operand of the first Linear's
  * weight gradient (dd_linear_wgrad); the hidden range is split as in the forward, the partials (dd_mlp_train_bwd_workspace_bytes(M, C,
  * splits) bytes, 16-byte aligned, private to the call's stream) folded in split order: no atomics, no zero-fill, bit-reproducible for a
- * given split count.  All three refuse C != 224; the two kernels refuse M > 2^19, splits > 42, a short workspace, a pointer that is not
- * 16-byte aligned and products outside {6, 3, 1}. */
+ * given split count.  dd_mlp_train_pack refuses C != 224 and dd_mlp_train_pack_narrow anything but 64 and 128; the two kernels refuse
+ * another width, M > 2^19, splits > 42, a short workspace, a pointer that is not 16-byte aligned and products outside {6, 3, 1}. */
 int dd_mlp_train_pack(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden, void* pack_fwd1,
                       void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream);
 int dd_mlp_train_fwd(const float* x, const void* pack_fwd1, const void* pack_fwd2_fused, const float* b1, const float* b2, int M, int C, int products,
                      int splits, float* y, float* h, float* d, void* workspace, size_t workspace_bytes, void* stream);
+int dd_mlp_train_pack_narrow(const float* w1, long long s1_n, long long s1_k, const float* w2, long long s2_n, long long s2_k, int C, int hidden,
+                             void* pack_fwd1, void* pack_fwd2_fused, void* pack_bwd2, void* pack_bwd1_fused, void* stream);
 size_t dd_mlp_train_bwd_workspace_bytes(int M, int C, int splits);
 int dd_mlp_train_bwd(const float* g, const float* d, const void* pack_bwd2, const void* pack_bwd1_fused, int M, int C, int products, int splits, float* dx,
                      float* gpre, void* workspace, size_t workspace_bytes, void* stream);
