@@ -98,19 +98,8 @@ def test_loader_contract_host_and_device_modes(tmp_path):
 
 def test_pyramid_weights_match_torch_on_cpu():
     """The tap set / weights dd_pyramid_down2 uses (8 taps 2i-3..2i+4, Keys a=-0.5 at (t-3.5)/2, clipped taps renormalised),
-    restated in numpy, reproduce F.interpolate(bicubic, antialias=True) on the CPU -- borders included."""
-    def cubic(x):
-        x = abs(x)
-        return (1.5 * x - 2.5) * x * x + 1 if x < 1 else (((-0.5 * x + 2.5) * x - 4) * x + 2 if x < 2 else 0.0)
-
-    def down(v):
-        n = v.shape[-1]
-        out = np.zeros(v.shape[:-1] + (n // 2,))
-        for i in range(n // 2):
-            taps = [(2 * i - 3 + t, cubic((t - 3.5) * 0.5)) for t in range(8) if 0 <= 2 * i - 3 + t < n]
-            tot = sum(w for _, w in taps)
-            out[..., i] = sum(v[..., j] * w for j, w in taps) / tot
-        return out
+    restated in numpy (tests/input_case.py), reproduce F.interpolate(bicubic, antialias=True) on the CPU -- borders included."""
+    from input_case import down2_last_axis as down
 
     x = torch.rand(1, 1, 12, 20, dtype=torch.float64)
     want = torch.nn.functional.interpolate(x, (6, 10), mode="bicubic", align_corners=False, antialias=True).numpy()
