@@ -218,3 +218,169 @@ extern "C" int dd_lidar_depth_points(const float* points, long long n_total, con
   }
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// nuScenes preparation (reference prepare_data/nuScenes.py:157-244; DESIGN 4.22, hipops/lidar.py pose_points_host / box_fit_host).
+//
+// dd_lidar_pose_points: every point of a batch of scans carried sensor -> ego (lidar time) -> global -> ego (camera time) -> camera,
+// one rigid step after the other as the reference applies them (never folded into one matrix), in float64, unfused, every dot
+// product left to right: rotate p' = R p with p'_k = (R[k,0] x + R[k,1] y) + R[k,2] z, translate p' = p + t or p - t.  The global
+// point is kept after the second step; pixel u = a_0 / a_2, v = a_1 / a_2 with a = K p_cam summed the same way, depth = z_cam; kept
+// where depth > 1, 1 < u < W - 1 and 1 < v < H - 1 (false for NaN).  Kept rows [u, v, depth, gx, gy, gz] are compacted in scan order
+// with the scheme of the KITTI rows above: block counts, one scan per job, rank by ballot -- the projection is computed twice with
+// the same code instead of being stored between the two launches.  Three launches per DL_CHUNK scans, no atomics.
+//
+// dd_box_fit: for every movable panoptic label of a key frame (its points contiguous: seg[l] .. seg[l + 1] - 1) and every
+// annotation box of the same category, the number of its points strictly inside the box (get_intersect_fraction's three dot-product
+// tests), and per label the first box with the strictly greatest count.  One launch, one workgroup per label, its four waves take
+// the boxes in turn; counts are sums of ballot popcounts in integers, the four waves' bests combine in box order: no atomics,
+// the same words every run.
+namespace dd {
+
+constexpr int DP_STRIDE = 64;       // doubles per scan: R1[9] t1[3] R2[9] t2[3] t3[3] R3[9] t4[3] R4[9] K[9] W H, 5 unused
+constexpr int BF_STRIDE = 16;       // doubles per box: p1[3] i[3] j[3] k[3] i.i j.j k.k, 1 unused
+
+__device__ __forceinline__ void dp_rotate(const double* __restrict__ R, double& x, double& y, double& z) {
+  const double a = (R[0] * x + R[1] * y) + R[2] * z;
+  const double b = (R[3] * x + R[4] * y) + R[5] * z;
+  const double c = (R[6] * x + R[7] * y) + R[8] * z;
+  x = a, y = b, z = c;
+}
+
+// the six values of one point; true where the reference's mask keeps it
+__device__ __forceinline__ bool dp_point(const float4 pt, const double* __restrict__ q, double* __restrict__ o) {
+  double x = (double)pt.x, y = (double)pt.y, z = (double)pt.z;
+  dp_rotate(q, x, y, z);
+  x = x + q[9], y = y + q[10], z = z + q[11];
+  dp_rotate(q + 12, x, y, z);
+  x = x + q[21], y = y + q[22], z = z + q[23];
+  o[3] = x, o[4] = y, o[5] = z;
+  x = x - q[24], y = y - q[25], z = z - q[26];
+  dp_rotate(q + 27, x, y, z);
+  x = x - q[36], y = y - q[37], z = z - q[38];
+  dp_rotate(q + 39, x, y, z);
+  const double depth = z;
+  dp_rotate(q + 48, x, y, z);
+  const double u = x / z, v = y / z;
+  o[0] = u, o[1] = v, o[2] = depth;
+  return depth > 1.0 && u > 1.0 && u < q[57] - 1.0 && v > 1.0 && v < q[58] - 1.0;
+}
+
+__global__ __launch_bounds__(DL_NT) void pose_count_kernel(const float4* __restrict__ points, DLScans sc, const double* __restrict__ params, int NBLK,
+                                                           int* __restrict__ blkcnt) {
+  const int s = blockIdx.y, base = sc.off[s], n = sc.off[s + 1] - base;
+  const int i = blockIdx.x * DL_NT + threadIdx.x;
+  double o[6];
+  const bool keep = i < n && dp_point(points[(size_t)base + i], params + (size_t)s * DP_STRIDE, o);
+  const int total = __syncthreads_count(keep);
+  if (threadIdx.x == 0) blkcnt[(size_t)s * NBLK + blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(DL_NT) void pose_rows_kernel(const float4* __restrict__ points, DLScans sc, const double* __restrict__ params, int NBLK,
+                                                          const int* __restrict__ blkoff, double* __restrict__ rows) {
+  __shared__ int wave_total[DL_NT / 64];
+  const int s = blockIdx.y, base = sc.off[s], n = sc.off[s + 1] - base;
+  const int i = blockIdx.x * DL_NT + threadIdx.x;
+  double o[6];
+  const bool keep = i < n && dp_point(points[(size_t)base + i], params + (size_t)s * DP_STRIDE, o);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(keep);
+  if (lane == 0) wave_total[wave] = __popcll(m);
+  __syncthreads();
+  if (!keep) return;
+  int rank = __popcll(m & ((1ull << lane) - 1ull));
+  for (int k = 0; k < wave; ++k) rank += wave_total[k];
+  double* out = rows + 6 * ((size_t)base + blkoff[(size_t)s * NBLK + blockIdx.x] + rank);      // < base + n: a scan has at most n rows
+#pragma unroll
+  for (int k = 0; k < 6; ++k) out[k] = o[k];
+}
+
+__global__ __launch_bounds__(DL_NT) void box_fit_kernel(const double* __restrict__ pts, int n_points, const int* __restrict__ seg,
+                                                        const int* __restrict__ label_cat, const double* __restrict__ boxes,
+                                                        const int* __restrict__ box_cat, int B, int* __restrict__ counts, int* __restrict__ best) {
+  __shared__ int s_cnt[DL_NT / 64], s_box[DL_NT / 64];
+  const int l = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lo = min(max(seg[l], 0), n_points), n = min(max(seg[l + 1], lo), n_points) - lo;
+  const int cat = label_cat[l];
+  int bc = 0, bb = -1;
+  for (int b = wave; b < B; b += DL_NT / 64) {
+    int c = -1;                                                   // a box of another category is not counted
+    if (box_cat[b] == cat) {
+      const double* q = boxes + (size_t)b * BF_STRIDE;
+      c = 0;
+      for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        bool in = false;
+        if (i < n) {
+          const double* p = pts + 3 * ((size_t)lo + i);
+          const double x = p[0] - q[0], y = p[1] - q[1], z = p[2] - q[2];
+          const double vi = (x * q[3] + y * q[4]) + z * q[5];
+          const double vj = (x * q[6] + y * q[7]) + z * q[8];
+          const double vk = (x * q[9] + y * q[10]) + z * q[11];
+          in = 0.0 < vi && vi < q[12] && 0.0 < vj && vj < q[13] && 0.0 < vk && vk < q[14];
+        }
+        c += __popcll(__ballot(in));
+      }
+      if (c > bc) bc = c, bb = b;                                 // ascending b: the first of equal counts stays
+    }
+    if (lane == 0) counts[(size_t)l * B + b] = c;
+  }
+  if (lane == 0) s_cnt[wave] = bc, s_box[wave] = bb;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 0; w < DL_NT / 64; ++w)
+      if (s_box[w] >= 0 && (s_cnt[w] > bc || (s_cnt[w] == bc && s_box[w] < bb))) bc = s_cnt[w], bb = s_box[w];
+    best[2 * l] = bb, best[2 * l + 1] = bc;
+  }
+}
+
+}  // namespace dd
+
+extern "C" size_t dd_lidar_pose_points_workspace_bytes(int S, long long n_max) {
+  if (S < 1 || n_max < 0 || n_max > 2147483647ll - DL_NT) return 0;
+  const long long nblk = n_max > 0 ? (n_max + DL_NT - 1) / DL_NT : 1;
+  return (size_t)(S < DL_CHUNK ? S : DL_CHUNK) * (size_t)nblk * 4;
+}
+
+extern "C" int dd_lidar_pose_points(const float* points, long long n_total, const int32_t* offsets, int S, const double* params, int32_t* counts,
+                                    double* rows, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!points || !offsets || !params || !counts || !rows || !workspace) return (int)hipErrorInvalidValue;
+  if (S < 1 || n_total < 0 || n_total > 2147483647ll - DL_NT) return (int)hipErrorInvalidValue;
+  if (offsets[0] != 0 || (long long)offsets[S] != n_total) return (int)hipErrorInvalidValue;
+  long long longest = 0;
+  for (int s = 0; s < S; ++s) {
+    if (offsets[s + 1] < offsets[s]) return (int)hipErrorInvalidValue;
+    if (offsets[s + 1] - offsets[s] > longest) longest = offsets[s + 1] - offsets[s];
+  }
+  if (workspace_bytes < dd_lidar_pose_points_workspace_bytes(S, longest)) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)points & 15u) || ((uintptr_t)params & 7u) || ((uintptr_t)rows & 7u) || ((uintptr_t)counts & 3u) || ((uintptr_t)workspace & 3u))
+    return (int)hipErrorInvalidValue;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int* blk = static_cast<int*>(workspace);
+  for (int s0 = 0; s0 < S; s0 += DL_CHUNK) {
+    const int ns = S - s0 < DL_CHUNK ? S - s0 : DL_CHUNK;
+    DLScans sc;
+    int n_max = 0;
+    for (int k = 0; k <= DL_CHUNK; ++k) sc.off[k] = offsets[s0 + (k < ns ? k : ns)];
+    for (int k = 0; k < ns; ++k) n_max = sc.off[k + 1] - sc.off[k] > n_max ? sc.off[k + 1] - sc.off[k] : n_max;
+    const int NBLK = n_max > 0 ? (n_max + DL_NT - 1) / DL_NT : 1;
+    const double* q = params + (size_t)s0 * DP_STRIDE;
+    hipLaunchKernelGGL(pose_count_kernel, dim3(NBLK, ns), dim3(DL_NT), 0, st, reinterpret_cast<const float4*>(points), sc, q, NBLK, blk);
+    hipLaunchKernelGGL(lidar_scan_kernel, dim3(ns), dim3(DL_NT), 0, st, blk, NBLK, counts + s0);
+    hipLaunchKernelGGL(pose_rows_kernel, dim3(NBLK, ns), dim3(DL_NT), 0, st, reinterpret_cast<const float4*>(points), sc, q, NBLK, blk, rows);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  return 0;
+}
+
+extern "C" int dd_box_fit(const double* points, int n_points, const int32_t* seg, const int32_t* label_cat, int L, const double* boxes,
+                          const int32_t* box_cat, int B, int32_t* counts, int32_t* best, void* stream) {
+  if (L < 0 || B < 0 || n_points < 0 || L > 2147483647 / (B > 0 ? B : 1)) return (int)hipErrorInvalidValue;
+  if (L == 0) return 0;
+  if (!seg || !label_cat || !best || (n_points > 0 && !points) || (B > 0 && (!boxes || !box_cat || !counts))) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)points & 7u) || ((uintptr_t)boxes & 7u)) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(box_fit_kernel, dim3(L), dim3(DL_NT), 0, static_cast<hipStream_t>(stream), points, n_points, seg, label_cat, boxes, box_cat, B,
+                     counts, best);
+  return (int)hipGetLastError();
+}

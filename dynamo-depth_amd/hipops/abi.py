@@ -175,6 +175,10 @@ def declare(lib):
         "dd_fill_contours": (i, [v, i, v, i, i, i, i, v, v]),
         "dd_lidar_depth_points_workspace_bytes": (z, [i, i, i, i]),
         "dd_lidar_depth_points": (i, [v, C.c_longlong, C.POINTER(C.c_int32), i, v, i, i, i, v, v, v, v, z, v]),
+        "dd_lidar_pose_points_workspace_bytes": (z, [i, C.c_longlong]),
+        "dd_lidar_pose_points": (i, [v, C.c_longlong, C.POINTER(C.c_int32), i, v, v, v, v, z, v]),
+        "dd_box_fit": (i, [v, i, v, v, i, v, v, i, v, v, v]),
+        "dd_resize_area": (i, [v, i, i, i, v, i, i, v, v, v, i, v, v, v, i, v]),
         "dd_vis_frame": (i, [v, v, v, v, v, v, v, v, f, f, i, i, C.POINTER(C.c_int), i, i, i, v, f, f, f, f, i, i, v, v, v, v]),
         "dd_vis_flow_tiles": (i, [v, v, C.POINTER(C.c_int), i, i, i, i, i, i, f, i, v, v]),
         "dd_export_depth": (i, [v, v, v, i, i, i, i, i, f, f, f, v, f, f, v, v, v, v]),
@@ -283,7 +287,7 @@ EXPORTED = (
     "dd_ssim", "dd_ssim_bwd", "dd_disp_to_depth", "dd_pose_matrix", "dd_pose_matrix_bwd",
     "dd_channel_sum_nhwc", "dd_channel_sum_workspace_bytes", "dd_reflect_pad1_nhwc", "dd_reflect_pad1_nhwc_bwd",
     "dd_dwconv3x3_nhwc", "dd_dwconv3x3_nhwc_bwd_data", "dd_dwconv3x3_nhwc_bwd_weight", "dd_dwconv3x3_workspace_bytes", "dd_conv3x3_cout1_bwd_data",
-    "dd_prepare_frames", "dd_prepare_frames_workspace_bytes", "dd_pyramid_down2", "dd_pack_rgb", "dd_depth_metrics", "dd_depth_metrics_workspace_bytes", "dd_depth_metrics_masked", "dd_depth_metrics_masked_workspace_bytes", "dd_depth_metrics_accumulate", "dd_odom_snippet_count", "dd_odom_snippets", "dd_motion_pr", "dd_fill_contours", "dd_lidar_depth_points", "dd_lidar_depth_points_workspace_bytes", "dd_vis_frame", "dd_vis_flow_tiles", "dd_export_depth", "dd_export_plane_u8", "dd_export_cloud_workspace_bytes", "dd_export_cloud", "dd_objects_workspace_bytes", "dd_objects", "dd_export_labels_u16", "dd_bn_act_fwd", "dd_bn_act_bwd", "dd_bn_workspace_bytes",
+    "dd_prepare_frames", "dd_prepare_frames_workspace_bytes", "dd_pyramid_down2", "dd_pack_rgb", "dd_depth_metrics", "dd_depth_metrics_workspace_bytes", "dd_depth_metrics_masked", "dd_depth_metrics_masked_workspace_bytes", "dd_depth_metrics_accumulate", "dd_odom_snippet_count", "dd_odom_snippets", "dd_motion_pr", "dd_fill_contours", "dd_lidar_depth_points", "dd_lidar_depth_points_workspace_bytes", "dd_lidar_pose_points", "dd_lidar_pose_points_workspace_bytes", "dd_box_fit", "dd_resize_area", "dd_vis_frame", "dd_vis_flow_tiles", "dd_export_depth", "dd_export_plane_u8", "dd_export_cloud_workspace_bytes", "dd_export_cloud", "dd_objects_workspace_bytes", "dd_objects", "dd_export_labels_u16", "dd_bn_act_fwd", "dd_bn_act_bwd", "dd_bn_workspace_bytes",
     "dd_bn_act_fwd_t", "dd_bn_act_bwd_t", "dd_channel_sum_nhwc_t", "dd_reflect_pad1_nhwc_t", "dd_reflect_pad1_nhwc_bwd_t", "dd_up_cat_pad_t", "dd_up_cat_pad_bwd_t",
     "dd_layer_norm_fwd", "dd_layer_norm_bwd", "dd_layer_norm_workspace_bytes", "dd_layer_scale_bwd", "dd_layer_scale_workspace_bytes",
     "dd_jpeg_workspace_bytes", "dd_jpeg_decode", "dd_resize_workspace_bytes", "dd_resize_bicubic", "dd_layer_norm_fwd_t", "dd_layer_norm_bwd_t", "dd_layer_scale_bwd_t", "dd_layer_scale_fwd_t", "dd_dwconv3x3_nhwc_t", "dd_dwconv3x3_nhwc_bwd_data_t",

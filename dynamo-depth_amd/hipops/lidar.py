@@ -17,7 +17,11 @@ ignored), one matrix `P` (float64 3x4) and an image H x W with W >= 2:
             bucket keeps its map value
   rows      the pixels with map > 0 in row-major order as float64 rows [r, c, d]
 
-`i` counts the kept points in file order."""
+`i` counts the kept points in file order.
+
+Below the KITTI part: the nuScenes preparation's pose chain (`pose_points_host`, `pose_points`; csrc/dd_lidar.hip dd_lidar_pose_points) and
+the key frames' box fit (`box_fit_host`, `box_fit`, `motion_labels`; dd_box_fit), DESIGN 4.22, with pyquaternion's rotation matrix and the
+devkit's box corners written out."""
 import ctypes
 import os
 
@@ -124,6 +128,208 @@ def depth_points(points, offsets, P, H, W, return_maps=False):
                                       abi.ptr(rows), abi.ptr(maps), abi.ptr(work), need, L.current_stream()), "dd_lidar_depth_points")
     rows = rows[:C * n_total]
     return (rows, counts, maps) if return_maps else (rows, counts)
+
+
+POSE_STRIDE = 64        # doubles per scan of dd_lidar_pose_points' params
+BOX_STRIDE = 16         # doubles per box of dd_box_fit
+
+
+def quaternion_matrix(q):
+    """float64 (3, 3) rotation matrix of the quaternion (w, x, y, z), normalised first: pyquaternion's `Quaternion(q).rotation_matrix`
+    written out (the lower-right block of its left and conjugate-right product matrices)."""
+    q = np.asarray(q, dtype=np.float64).reshape(4)
+    norm = np.sqrt(np.dot(q, q))
+    if norm > 0:
+        q = q / norm
+    w, x, y, z = q
+    return np.array([[w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                     [2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x)],
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z]], dtype=np.float64)
+
+
+def transform_matrix(translation, rotation):
+    """The devkit's transform_matrix(translation, Quaternion(rotation)): float64 (4, 4)."""
+    T = np.eye(4)
+    T[:3, :3] = quaternion_matrix(rotation)
+    T[:3, 3] = np.asarray(translation, dtype=np.float64)
+    return T
+
+
+def pose_params(lidar_cs, lidar_pose, cam_pose, cam_cs, K, W, H):
+    """The POSE_STRIDE doubles of one scan from four records with `rotation` (w, x, y, z) and `translation`, the 3x3 intrinsics and
+    the image size: the matrices as reference nuScenes.py:161-180 applies them (the last two transposed)."""
+    out = np.zeros(POSE_STRIDE, dtype=np.float64)
+    out[0:9] = quaternion_matrix(lidar_cs["rotation"]).reshape(-1)
+    out[9:12] = lidar_cs["translation"]
+    out[12:21] = quaternion_matrix(lidar_pose["rotation"]).reshape(-1)
+    out[21:24] = lidar_pose["translation"]
+    out[24:27] = cam_pose["translation"]
+    out[27:36] = quaternion_matrix(cam_pose["rotation"]).T.reshape(-1)
+    out[36:39] = cam_cs["translation"]
+    out[39:48] = quaternion_matrix(cam_cs["rotation"]).T.reshape(-1)
+    out[48:57] = np.asarray(K, dtype=np.float64).reshape(-1)
+    out[57], out[58] = W, H
+    return out
+
+
+def _rotate(R, p):
+    R = R.reshape(3, 3)
+    return [(R[k, 0] * p[0] + R[k, 1] * p[1]) + R[k, 2] * p[2] for k in range(3)]
+
+
+def pose_points_host(points, params):
+    """The definition of dd_lidar_pose_points for one scan: points float32 (n, >= 3), params from `pose_params` -> (rows float64
+    (m, 6) [u, v, depth, gx, gy, gz] of the kept points in scan order, all float64 (n, 6), kept bool (n,)).  float64 from the first
+    step on, every dot product summed left to right: the devkit keeps its cloud in float32 between the steps, which is not
+    reproduced."""
+    q = np.asarray(params, dtype=np.float64).reshape(POSE_STRIDE)
+    pts = np.asarray(points, dtype=np.float32)
+    p = [pts[:, k].astype(np.float64) for k in range(3)]
+    with np.errstate(all="ignore"):
+        p = [c + t for c, t in zip(_rotate(q[0:9], p), q[9:12])]
+        p = [c + t for c, t in zip(_rotate(q[12:21], p), q[21:24])]
+        g = p
+        p = _rotate(q[27:36], [c - t for c, t in zip(p, q[24:27])])
+        p = _rotate(q[39:48], [c - t for c, t in zip(p, q[36:39])])
+        depth = p[2]
+        a = _rotate(q[48:57], p)
+        u, v = a[0] / a[2], a[1] / a[2]
+        kept = (depth > 1.0) & (u > 1.0) & (u < q[57] - 1.0) & (v > 1.0) & (v < q[58] - 1.0)
+    full = np.stack([u, v, depth, g[0], g[1], g[2]], axis=1)
+    return full[kept], full, kept
+
+
+def pose_points(points, offsets, params):
+    """points (n_total, 4) float32 and params (S, POSE_STRIDE) float64 on the GPU, offsets the S + 1 scan boundaries on the host ->
+    (rows (n_total, 6) float64, counts (S, 1) int32) on the GPU, laid out for `split_rows`.  One call on the current stream."""
+    import torch
+
+    from . import abi
+    from . import lib as L
+    if not (torch.is_tensor(points) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 4):
+        raise L.DynamoHipError("pose_points takes (n_total, 4) float32 points on the GPU")
+    if not (torch.is_tensor(params) and params.is_cuda and params.dtype == torch.float64 and params.dim() == 2 and params.shape[1] == POSE_STRIDE):
+        raise L.DynamoHipError("pose_points takes (S, {}) float64 parameters on the GPU".format(POSE_STRIDE))
+    off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    n_total, S = int(points.shape[0]), off.size - 1
+    if S < 1 or S != int(params.shape[0]) or off.min() < 0 or off.max() > 2 ** 31 - 1:
+        raise L.DynamoHipError("pose_points: offsets must hold S + 1 >= 2 row numbers, one parameter row per scan")
+    longest = int(np.diff(off).max())
+    off = off.astype(np.int32)
+    lib = L.load()
+    points, params = points.contiguous(), params.contiguous()
+    dev = points.device
+    src = points if n_total > 0 else torch.zeros((1, 4), dtype=torch.float32, device=dev)
+    rows = torch.empty((max(n_total, 1), 6), dtype=torch.float64, device=dev)
+    counts = torch.empty((S, 1), dtype=torch.int32, device=dev)
+    need = int(lib.dd_lidar_pose_points_workspace_bytes(S, max(longest, 0)))
+    work = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+    L.check(lib.dd_lidar_pose_points(abi.ptr(src), n_total, off.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), S, abi.ptr(params), abi.ptr(counts),
+                                     abi.ptr(rows), abi.ptr(work), need, L.current_stream()), "dd_lidar_pose_points")
+    return rows[:n_total], counts
+
+
+def box_corners(center, wlh, rotation):
+    """float64 (8, 3): the corners of an annotation box in the devkit's `Box.corners()` order (x forward, y left, z up; the first
+    four have x > 0), transposed as the reference uses them."""
+    w, l, h = (float(v) for v in wlh)
+    x = l / 2 * np.array([1, 1, 1, 1, -1, -1, -1, -1], dtype=np.float64)
+    y = w / 2 * np.array([1, -1, -1, 1, 1, -1, -1, 1], dtype=np.float64)
+    z = h / 2 * np.array([1, 1, -1, -1, 1, 1, -1, -1], dtype=np.float64)
+    corners = np.dot(quaternion_matrix(rotation), np.vstack((x, y, z)))
+    return (corners + np.asarray(center, dtype=np.float64).reshape(3, 1)).T
+
+
+def box_params(corners):
+    """(B, 8, 3) corners -> (B, BOX_STRIDE) float64: p1, i = p2 - p1, j = p4 - p1, k = p5 - p1, i.i, j.j, k.k (sums left to right)."""
+    c = np.asarray(corners, dtype=np.float64).reshape(-1, 8, 3)
+    out = np.zeros((c.shape[0], BOX_STRIDE), dtype=np.float64)
+    out[:, 0:3] = c[:, 0]
+    for n, corner in enumerate((1, 3, 4)):
+        e = c[:, corner] - c[:, 0]
+        out[:, 3 + 3 * n:6 + 3 * n] = e
+        out[:, 12 + n] = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2]
+    return out
+
+
+def box_fit_host(points, seg, label_cat, boxes, box_cat):
+    """The definition of dd_box_fit: points float64 (n, 3) with label l at rows seg[l] .. seg[l + 1] - 1, boxes from `box_params` ->
+    (counts int32 (L, B), -1 where the categories differ; best int32 (L, 2) [first box with the strictly greatest count or -1, count])."""
+    pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    seg = np.asarray(seg, dtype=np.int64).reshape(-1)
+    boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, BOX_STRIDE)
+    L, B = seg.size - 1, boxes.shape[0]
+    counts = np.full((L, B), -1, dtype=np.int32)
+    best = np.zeros((L, 2), dtype=np.int32)
+    best[:, 0] = -1
+    for l in range(L):
+        p = pts[seg[l]:seg[l + 1]]
+        for b in range(B):
+            if int(box_cat[b]) != int(label_cat[l]):
+                continue
+            q = boxes[b]
+            d = [p[:, k] - q[k] for k in range(3)]
+            dots = [(d[0] * q[3 + 3 * n] + d[1] * q[4 + 3 * n]) + d[2] * q[5 + 3 * n] for n in range(3)]
+            inside = np.ones(p.shape[0], dtype=bool)
+            for n in range(3):
+                inside &= (0.0 < dots[n]) & (dots[n] < q[12 + n])
+            counts[l, b] = int(inside.sum())
+            if counts[l, b] > best[l, 1]:
+                best[l] = (b, counts[l, b])
+    return counts, best
+
+
+def box_fit(points, seg, label_cat, boxes, box_cat):
+    """`box_fit_host` on the device from host arrays, one launch: (counts (L, B), best (L, 2)) as int32 numpy arrays."""
+    import torch
+
+    from . import abi
+    from . import lib as L_
+    pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+    seg = np.ascontiguousarray(np.asarray(seg, dtype=np.int32).reshape(-1))
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64).reshape(-1, BOX_STRIDE))
+    n_labels, B = seg.size - 1, boxes.shape[0]
+    if n_labels < 0 or len(label_cat) != n_labels or len(box_cat) != B or (n_labels and (seg[0] != 0 or seg[-1] != pts.shape[0] or (np.diff(seg) < 0).any())):
+        raise L_.DynamoHipError("box_fit: seg must run from 0 to the number of points, one category per label and per box")
+    counts = torch.full((max(n_labels * B, 1),), -1, dtype=torch.int32, device="cuda")
+    best = torch.zeros((max(n_labels, 1), 2), dtype=torch.int32, device="cuda")
+    if n_labels:
+        def up(a, dtype, fill):
+            a = np.ascontiguousarray(np.asarray(a, dtype=dtype))
+            return torch.from_numpy(a if a.size else np.full(fill, 0, dtype=dtype)).cuda()
+        d_pts, d_boxes = up(pts, np.float64, (1, 3)), up(boxes, np.float64, (1, BOX_STRIDE))
+        d_seg, d_lc, d_bc = up(seg, np.int32, 2), up(np.asarray(label_cat).reshape(-1), np.int32, 1), up(np.asarray(box_cat).reshape(-1), np.int32, 1)
+        L_.check(L_.load().dd_box_fit(abi.ptr(d_pts), pts.shape[0], abi.ptr(d_seg), abi.ptr(d_lc), n_labels, abi.ptr(d_boxes), abi.ptr(d_bc), B,
+                                      abi.ptr(counts), abi.ptr(best), L_.current_stream()), "dd_box_fit")
+    return counts[:n_labels * B].cpu().numpy().reshape(n_labels, B), best[:n_labels].cpu().numpy()
+
+
+def motion_labels(panoptic, points, boxes, movable_cats, fit=box_fit_host):
+    """Reference nuScenes.py:218-243 for one key frame.  panoptic uint16 (n,) labels (category * 1000 + instance) and points float64
+    (n, 3) of the kept points; boxes a list of (token, category index, corners (8, 3), moving bool) in the annotations' order ->
+    (motion_label uint8 (n,): 0 not movable, 1 in motion, 2 static movable, 3 no box found; panoptic2ann {label: {token, fit}})."""
+    panoptic = np.asarray(panoptic)
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    motion = np.full(panoptic.shape, 3, dtype=np.uint8)
+    uniq = np.unique(panoptic)
+    movable = [u for u in uniq if int(u) // 1000 in movable_cats]
+    for u in uniq:
+        if int(u) // 1000 not in movable_cats:
+            motion[panoptic == u] = 0
+    panoptic2ann = {}
+    if movable:
+        index = [np.nonzero(panoptic == u)[0] for u in movable]
+        seg = np.concatenate([[0], np.cumsum([i.size for i in index])]).astype(np.int32)
+        corners = np.array([b[2] for b in boxes], dtype=np.float64).reshape(-1, 8, 3)
+        _, best = fit(points[np.concatenate(index)], seg, [int(u) // 1000 for u in movable], box_params(corners), [int(b[1]) for b in boxes])
+        for l, u in enumerate(movable):
+            b, count = int(best[l][0]), int(best[l][1])
+            if b < 0:
+                panoptic2ann[u] = {"token": None, "fit": 0}
+                continue
+            motion[index[l]] = 1 if boxes[b][3] else 2
+            panoptic2ann[u] = {"token": boxes[b][0], "fit": np.float64(count) / np.float64(index[l].size)}
+    return motion, panoptic2ann
 
 
 def split_rows(rows, counts, offsets):

@@ -284,6 +284,17 @@ int dd_resize_bicubic(const unsigned char* src, int n_images, int Hs, int Ws, un
                       const int32_t* h_bounds, const int32_t* h_coef, int h_ksize, const int32_t* v_bounds, const int32_t* v_coef, int v_ksize,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* Area-weighted down-sample, OpenCV's INTER_AREA for any down-scale (reference prepare_data/nuScenes.py:152, 1600x900 -> 512x288):
+ * src (n,Hs,Ws,3) uint8, 16-byte aligned -> dst (n,Hd,Wd,3) uint8 with Hd <= Hs and Wd <= Ws.  Per axis the host builds
+ * (hipops/resize.py area_table): start [D] int32 first source index, count [D] int32 taps, weight (D,taps) float32 padded with
+ * zeros.  dst = the separable weighted sum, columns first, then rows, in fp32 with one fused multiply-add per tap in ascending tap
+ * order, rounded half to even, saturated; DESIGN 4.22.  One launch; source rows staged through LDS, no atomics, no workspace.
+ * hipErrorInvalidValue (1): a NULL pointer, a non-positive size, an up-scale, more than 65535 images, taps above 1024, Hs*Ws*3 above
+ * 2^31-1, a scale so large that one destination column's strip does not fit the staging buffer, a misaligned src. */
+int dd_resize_area(const unsigned char* src, int n_images, int Hs, int Ws, unsigned char* dst, int Hd, int Wd, const int32_t* h_start,
+                   const int32_t* h_count, const float* h_weight, int h_taps, const int32_t* v_start, const int32_t* v_count,
+                   const float* v_weight, int v_taps, void* stream);
+
 /* ---- operator-level entry points: the tools.py modules one by one (forward; *_bwd = autograd) ---- */
 
 /* tools.BackprojectDepth.forward (tools.py:191-197): depth (B,1,h,w), inv_K (B,4,4) -> points (B,4,h*w) */
@@ -457,6 +468,35 @@ int dd_fill_contours(const int16_t* vertices, int v_cap, const int32_t* contours
 size_t dd_lidar_depth_points_workspace_bytes(int S, int C, int H, int W);
 int dd_lidar_depth_points(const float* points, long long n_total, const int32_t* offsets, int S, const double* P, int C, int H, int W,
                           int32_t* counts, double* rows, float* maps, void* workspace, size_t workspace_bytes, void* stream);
+
+/* nuScenes LiDAR lists (reference prepare_data/nuScenes.py:157-198): every point of a batch of scans carried sensor -> ego (lidar
+ * time) -> global -> ego (camera time) -> camera by four rigid steps applied one after the other in float64 (unfused, each dot
+ * product left to right), projected with the 3x3 intrinsics and kept where depth > 1, 1 < u < W-1, 1 < v < H-1; DESIGN 4.22,
+ * hipops/lidar.py pose_points_host restates it in numpy.
+ * points (n_total,4) float32, 16-byte aligned, column 3 ignored; offsets [S+1] int32 on the HOST as for dd_lidar_depth_points.
+ * params (S,64) float64 on the device, per scan: R1[9] t1[3] R2[9] t2[3] t3[3] R3[9] t4[3] R4[9] K[9] W H and 5 unused words, row-major
+ *   matrices as they are applied: p = R1 p + t1; p = R2 p + t2 (the global point); p = R3 (p - t3); p = R4 (p - t4); a = K p.
+ * counts [S] int32: kept points per scan, every one written.
+ * rows (n_total,6) float64 [u, v, depth, gx, gy, gz]: scan s writes the first counts[s] rows from row offsets[s], in scan order;
+ *   the rest of its segment is left as it was.
+ * workspace: dd_lidar_pose_points_workspace_bytes(S, longest scan), 4-byte aligned.  3 launches per 16 scans, no atomics.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer, S < 1, n_total negative or above 2^31-257, bad offsets, a workspace that
+ * is too small, a misaligned pointer. */
+size_t dd_lidar_pose_points_workspace_bytes(int S, long long n_max);
+int dd_lidar_pose_points(const float* points, long long n_total, const int32_t* offsets, int S, const double* params, int32_t* counts,
+                         double* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Motion labels of a nuScenes key frame (reference prepare_data/nuScenes.py:209-244, get_intersect_fraction): per movable panoptic
+ * label the number of its points strictly inside every annotation box of its category, and the first box with the strictly
+ * greatest count; hipops/lidar.py box_fit_host restates it.  All pointers on the device.
+ * points (n_points,3) float64, the points of label l contiguous: rows seg[l] .. seg[l+1]-1 (seg [L+1] int32, clamped to n_points).
+ * label_cat [L], box_cat [B] int32 category indices.  boxes (B,16) float64: p1[3], i = p2-p1, j = p4-p1, k = p5-p1, i.i, j.j, k.k,
+ *   one unused word; a point p is inside where 0 < (p-p1).i < i.i and the same for j and k, sums left to right, unfused.
+ * counts (L,B) int32: points of l inside b, -1 where the categories differ.  best (L,2) int32: [box, count], box -1 and count 0
+ *   where no box of the category holds a point.  One launch, integer sums in a fixed order; L == 0 launches nothing.
+ * hipErrorInvalidValue (1): negative sizes, L*B above 2^31-1, a NULL pointer that would be read or written, a misaligned pointer. */
+int dd_box_fit(const double* points, int n_points, const int32_t* seg, const int32_t* label_cat, int L, const double* boxes,
+               const int32_t* box_cat, int B, int32_t* counts, int32_t* best, void* stream);
 
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
@@ -834,7 +874,7 @@ int dd_export_cloud(const float* disp, const float* disp_flipped, const float* l
                     float max_depth, float max_range, float edge, float motion_thresh, int stride, void* records, long long* offsets,
                     void* workspace, size_t workspace_bytes, void* stream);
 
-/* Moving objects as labelled instances (predict.py --save objects; csrc/dd_objects.hip, DESIGN 4.21): the connected components of the
+/* Moving objects as labelled instances (predict.py --save objects; csrc/dd_objects.hip, DESIGN 4.22): the connected components of the
  * thresholded motion mask and one table row per object.  hipops/objects.py objects_host is the definition in numpy.
  * All maps at the network's resolution: motion_mask (B,h,w), disp, disp_flipped, l_mask as dd_export_depth, complete_flow (B,3,h,w),
  * ts (B), pose (B,3,4) row-major [R | t] of the transform from frame 0 to the neighbouring frame.  fx, fy, cx, cy: in pixels of the
