@@ -413,17 +413,3 @@ extern "C" int dd_bn_act_bwd_t(const void* x, const void* g_out, const void* out
                     static_cast<float*>(workspace), static_cast<hipStream_t>(stream));
   return (int)hipGetLastError();
 }
-
-extern "C" int dd_bn_act_fwd(const float* x, const float* residual, long long rows, int C, const float* gamma, const float* beta, float eps,
-                             float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act,
-                             float* out, void* workspace, size_t workspace_bytes, void* stream) {
-  return dd_bn_act_fwd_t(x, residual, rows, C, gamma, beta, eps, momentum, running_mean, running_var, save_mean, save_invstd, act, out, 0, workspace,
-                         workspace_bytes, stream);
-}
-
-extern "C" int dd_bn_act_bwd(const float* x, const float* g_out, const float* out, long long rows, int C, const float* gamma, const float* beta,
-                             const float* save_mean, const float* save_invstd, int act, float* g_x, float* g_residual, float* g_gamma,
-                             float* g_beta, void* workspace, size_t workspace_bytes, void* stream) {
-  return dd_bn_act_bwd_t(x, g_out, out, rows, C, gamma, beta, save_mean, save_invstd, act, g_x, g_residual, g_gamma, g_beta, 0, workspace,
-                         workspace_bytes, stream);
-}

@@ -160,15 +160,6 @@ extern "C" int dd_dwconv3x3_nhwc_bwd_data_t(const void* g_out, const float* weig
   return launch_dw(true, g_out, weight, B, H, W, C, dilation, g_x, dtype, stream);
 }
 
-extern "C" int dd_dwconv3x3_nhwc(const float* x, const float* weight, int B, int H, int W, int C, int dilation, float* out, void* stream) {
-  return launch_dw(false, x, weight, B, H, W, C, dilation, out, 0, stream);
-}
-
-extern "C" int dd_dwconv3x3_nhwc_bwd_data(const float* g_out, const float* weight, int B, int H, int W, int C, int dilation, float* g_x,
-                                          void* stream) {
-  return launch_dw(true, g_out, weight, B, H, W, C, dilation, g_x, 0, stream);
-}
-
 extern "C" size_t dd_dwconv3x3_workspace_bytes(int B, int H, int C) { return (size_t)B * H * 9 * C * sizeof(float); }
 
 template <typename T>
@@ -194,11 +185,6 @@ extern "C" int dd_dwconv3x3_nhwc_bwd_weight_t(const void* g_out, const void* x, 
   const int per = DW_NT / DW_FOLD;
   hipLaunchKernelGGL(dwconv3x3_wgrad_fold_kernel, dim3((9 * C + per - 1) / per), dim3(DW_NT), 0, s, partial, B * H, C, g_weight);
   return (int)hipGetLastError();
-}
-
-extern "C" int dd_dwconv3x3_nhwc_bwd_weight(const float* g_out, const float* x, int B, int H, int W, int C, int dilation, float* g_weight,
-                                            void* workspace, size_t workspace_bytes, void* stream) {
-  return dd_dwconv3x3_nhwc_bwd_weight_t(g_out, x, B, H, W, C, dilation, g_weight, workspace, workspace_bytes, 0, stream);
 }
 
 // ---- data gradient of a 3x3 convolution with ONE output channel (the disparity heads `dispconv`, reference

@@ -152,11 +152,6 @@ extern "C" int dd_layer_norm_fwd_t(const void* x, long long rows, int C, const f
   return (int)hipGetLastError();
 }
 
-extern "C" int dd_layer_norm_fwd(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, float* y,
-                                 float* mean, float* rstd, void* stream) {
-  return dd_layer_norm_fwd_t(x, rows, C, gamma, beta, eps, y, mean, rstd, 0, stream);
-}
-
 extern "C" int dd_layer_norm_bwd_t(const void* x, const void* g_out, const float* gamma, const float* mean, const float* rstd, long long rows, int C,
                                    void* g_x, float* g_gamma_beta, void* workspace, size_t workspace_bytes, int dtype, void* stream) {
   if (!x || !g_out || !gamma || !mean || !rstd || !g_x || !g_gamma_beta || !workspace || !ln_dims_ok(rows, C) || dtype < 0 || dtype > 2)
@@ -169,11 +164,6 @@ extern "C" int dd_layer_norm_bwd_t(const void* x, const void* g_out, const float
   const int n = 2 * C;
   hipLaunchKernelGGL(ln_fold_kernel, dim3((n + LN_NT / 64 - 1) / (LN_NT / 64)), dim3(LN_NT), 0, s, partial, blocks, n, g_gamma_beta);
   return (int)hipGetLastError();
-}
-
-extern "C" int dd_layer_norm_bwd(const float* x, const float* g_out, const float* gamma, const float* mean, const float* rstd, long long rows,
-                                 int C, float* g_x, float* g_gamma_beta, void* workspace, size_t workspace_bytes, void* stream) {
-  return dd_layer_norm_bwd_t(x, g_out, gamma, mean, rstd, rows, C, g_x, g_gamma_beta, workspace, workspace_bytes, 0, stream);
 }
 
 // ---- backward of the layer-scale residual of LiteMono's blocks: out = res + y * scale[b, c]  (scale = gamma * drop-path factor;
@@ -284,9 +274,4 @@ extern "C" int dd_layer_scale_bwd_t(const void* g_out, const void* y, const floa
   DD_DISPATCH_DTYPE(dtype, layer_scale_launch, g_out, y, scale, rows, C, lanes, per, g_y, partial, dim3(chunks, B), threads, s);
   hipLaunchKernelGGL(dd::layer_scale_fold_kernel, dim3((C + dd::LS_NT - 1) / dd::LS_NT, B), dim3(dd::LS_NT), 0, s, partial, chunks, C, g_scale);
   return (int)hipGetLastError();
-}
-
-extern "C" int dd_layer_scale_bwd(const float* g_out, const float* y, const float* scale, int B, int rows, int C, float* g_y, float* g_scale,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-  return dd_layer_scale_bwd_t(g_out, y, scale, B, rows, C, g_y, g_scale, workspace, workspace_bytes, 0, stream);
 }

@@ -528,10 +528,6 @@ extern "C" int dd_channel_sum_nhwc_t(const void* x, long long rows, int C, float
   return ops_err();
 }
 
-extern "C" int dd_channel_sum_nhwc(const float* x, long long rows, int C, float* out, float* workspace, void* stream) {
-  return dd_channel_sum_nhwc_t(x, rows, C, out, 0, workspace, stream);
-}
-
 template <typename T>
 static void reflect_pad_launch(const void* x, int B, int H, int W, int C, void* out, hipStream_t s) {
   hipLaunchKernelGGL(reflect_pad1_nhwc_kernel<T>, dim3(((W + 2) * C + PAD_NT - 1) / PAD_NT, H + 2, B), dim3(PAD_NT), 0, s, static_cast<const T*>(x), H, W, C,
@@ -553,12 +549,4 @@ extern "C" int dd_reflect_pad1_nhwc_bwd_t(const void* g_out, int B, int H, int W
   if (!g_out || !g_x || B < 1 || H < 4 || W < 4 || C < 1 || B > 65535 || H > 65535 || dtype < 0 || dtype > 2) return (int)hipErrorInvalidValue;
   DD_DISPATCH_DTYPE(dtype, reflect_pad_bwd_launch, g_out, B, H, W, C, g_x, static_cast<hipStream_t>(stream));
   return ops_err();
-}
-
-extern "C" int dd_reflect_pad1_nhwc(const float* x, int B, int H, int W, int C, float* out, void* stream) {
-  return dd_reflect_pad1_nhwc_t(x, B, H, W, C, out, 0, stream);
-}
-
-extern "C" int dd_reflect_pad1_nhwc_bwd(const float* g_out, int B, int H, int W, int C, float* g_x, void* stream) {
-  return dd_reflect_pad1_nhwc_bwd_t(g_out, B, H, W, C, g_x, 0, stream);
 }

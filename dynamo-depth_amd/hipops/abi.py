@@ -12,6 +12,7 @@ DD_MODE_RIGID, DD_MODE_FLOW, DD_MODE_FLOW_MASK = 0, 1, 2
 DD_PARTIAL_STRIDE = 40
 DD_SUMS_STRIDE = 8
 DD_OBJECTS_ROW = 22         # 32-bit words per row of dd_objects' table
+DD_DTYPE_F32, DD_DTYPE_F16, DD_DTYPE_BF16 = 0, 1, 2         # `dtype` of the element-typed (_t) entry points
 
 _fp = C.c_void_p        # device (or, for the host-math test library, host) float*
 
@@ -116,195 +117,166 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+_i, _f, _d, _v, _z, _ll = C.c_int, C.c_float, C.c_double, C.c_void_p, C.c_size_t, C.c_longlong
+
+# name -> (restype, argtypes): one entry per prototype of include/dynamo_hip.h, the only list of entry points on the Python side
+# (tests/test_abi.py holds it against the header, argument by argument)
+SIGNATURES = {
+    "dd_photo_loss": (_i, [C.POINTER(DDPhotoArgs), _v]),
+    "dd_photo_workspace_bytes": (_z, [C.POINTER(DDPhotoArgs)]),
+    "dd_photo_timing": (_i, [_i]),
+    "dd_photo_timing_read": (_i, [C.POINTER(C.c_float), C.POINTER(_i), _i]),
+    "dd_photo_loss_part": (_i, [C.POINTER(DDPhotoArgs), _v, _i]),
+    "dd_smooth_loss": (_i, [_v, _v, _i, _i, _i, _i, _i, _f, _v, _v, _v, _v]),
+    "dd_smooth_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_ground_loss": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _v, _v, _v, _v, _v]),
+    "dd_ground_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_resize_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dd_resize_bicubic": (_i, [_v, _i, _i, _i, _v, _v, _i, _i, _v, _v, _i, _v, _v, _i, _v, _z, _v]),
+    "dd_ground_candidates": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _f, _f, _f, _v, _v]),
+    "dd_ground_select": (_i, [_v, _v, _v, _i, _i, _i, _i, _f, _f, _f, _f, _f, _v, _v, _v, _v, _v, _v]),
+    "dd_ground_plane": (_i, [_v, _v, _i, _i, _i, _i, _i, _f, _f, _v, _v, _v, _v]),
+    "dd_assemble_losses": (_i, [_v, C.POINTER(DDAssembleArgs), _v, _v, _v]),
+    "dd_reg_losses_finish": (_i, [C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), _v, _v, _v]),
+    "dd_fused_loss": (_i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), _v, _v, _v]),
+    "dd_fused_loss_part": (_i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), _v, _v, _v, _i]),
+    "dd_fused_loss_supported": (_i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs)]),
+    "dd_reg_workspace_bytes": (_z, [C.POINTER(DDRegArgs)]),
+    "dd_jpeg_workspace_bytes": (_z, [_i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "dd_jpeg_decode": (_i, [_v, _ll, _v, _i, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _v, _v, _z, _v]),
+    "dd_backproject": (_i, [_v, _v, _i, _i, _i, _v, _v]),
+    "dd_backproject_bwd": (_i, [_v, _v, _i, _i, _i, _v, _v]),
+    "dd_project3d": (_i, [_v, _v, _v, _i, _i, _i, _f, _v, _v, _v]),
+    "dd_project3d_bwd": (_i, [_v, _v, _v, _v, _v, _i, _i, _i, _f, _v, _v, _v, _v]),
+    "dd_project3d_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_ssim": (_i, [_v, _v, _i, _i, _i, _i, _v, _v]),
+    "dd_ssim_bwd": (_i, [_v, _v, _v, _i, _i, _i, _i, _v, _v, _v]),
+    "dd_disp_to_depth": (_i, [_v, _z, _f, _f, _v, _v, _v]),
+    "dd_pose_matrix": (_i, [_v, _v, _i, _i, _v, _v]),
+    "dd_pose_matrix_bwd": (_i, [_v, _v, _v, _i, _i, _v, _v, _v]),
+    "dd_channel_sum_workspace_bytes": (_z, [_i]),
+    "dd_dwconv3x3_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_conv3x3_cout1_bwd_data": (_i, [_v, _v, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_prepare_frames": (_i, [_v, _v, _v, _i, _i, _i, _i, _v, _v, _v, _v]),
+    "dd_prepare_frames_workspace_bytes": (_z, [_i, _i]),
+    "dd_pyramid_down2": (_i, [_v, _i, _i, _i, _v, _v]),
+    "dd_pack_rgb": (_i, [_v, _i, _i, _i, _v, _v]),
+    "dd_depth_metrics": (_i, [_v, _i, _i, _i, _v, _v, _i, _v, C.POINTER(_d), _f, _f, _v, _v, _v, _z, _v]),
+    "dd_depth_metrics_workspace_bytes": (_z, [_i, _i]),
+    "dd_depth_metrics_masked": (_i, [_v, _i, _i, _i, _v, _v, _i, _v, C.POINTER(_d), _f, _f, _v, _i, _i, _v, _v, _v, _v, _z, _v]),
+    "dd_depth_metrics_masked_workspace_bytes": (_z, [_i, _i]),
+    "dd_depth_metrics_accumulate": (_i, [_v, _v, _i, _v, _v, _v]),
+    "dd_odom_snippet_count": (_i, [_i, _i]),
+    "dd_odom_snippets": (_i, [_v, _v, _i, _i, _v, _v, _v]),
+    "dd_motion_pr": (_i, [_v, _i, _i, _i, _v, _v, _i, _i, _v, _i, _i, _v, _v]),
+    "dd_fill_contours": (_i, [_v, _i, _v, _i, _i, _i, _i, _v, _v]),
+    "dd_lidar_depth_points_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_lidar_depth_points": (_i, [_v, _ll, C.POINTER(C.c_int32), _i, _v, _i, _i, _i, _v, _v, _v, _v, _z, _v]),
+    "dd_lidar_pose_points_workspace_bytes": (_z, [_i, _ll]),
+    "dd_lidar_pose_points": (_i, [_v, _ll, C.POINTER(C.c_int32), _i, _v, _v, _v, _v, _z, _v]),
+    "dd_box_fit": (_i, [_v, _i, _v, _v, _i, _v, _v, _i, _v, _v, _v]),
+    "dd_resize_area": (_i, [_v, _i, _i, _i, _v, _i, _i, _v, _v, _v, _i, _v, _v, _v, _i, _v]),
+    "dd_vis_frame": (_i, [_v, _v, _v, _v, _v, _v, _v, _v, _f, _f, _i, _i, C.POINTER(C.c_int), _i, _i, _i, _v, _f, _f, _f, _f, _i, _i, _v, _v, _v, _v]),
+    "dd_vis_flow_tiles": (_i, [_v, _v, C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i, _f, _i, _v, _v]),
+    "dd_export_depth": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _f, _f, _f, _v, _f, _f, _v, _v, _v, _v]),
+    "dd_export_plane_u8": (_i, [_v, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_export_cloud_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_export_cloud": (_i, [_v, _v, _v, _v, _v, _v, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _f, _f, _i, _v, _v, _v, _z, _v]),
+    "dd_objects_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_objects": (_i, [_v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _v, _v, _v, _v, _z, _v]),
+    "dd_export_labels_u16": (_i, [_v, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_bn_workspace_bytes": (_z, [_i]),
+    "dd_bn_act_fwd_t": (_i, [_v, _v, _ll, _i, _v, _v, _f, _f, _v, _v, _v, _v, _i, _v, _i, _v, _z, _v]),
+    "dd_bn_act_bwd_t": (_i, [_v, _v, _v, _ll, _i, _v, _v, _v, _v, _i, _v, _v, _v, _v, _i, _v, _z, _v]),
+    "dd_channel_sum_nhwc_t": (_i, [_v, _ll, _i, _v, _i, _v, _v]),
+    "dd_reflect_pad1_nhwc_t": (_i, [_v, _i, _i, _i, _i, _v, _i, _v]),
+    "dd_reflect_pad1_nhwc_bwd_t": (_i, [_v, _i, _i, _i, _i, _v, _i, _v]),
+    "dd_up_cat_pad_t": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _i, _v]),
+    "dd_up_cat_pad_bwd_t": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _v, _i, _v]),
+    "dd_layer_norm_workspace_bytes": (_z, [_i]),
+    "dd_layer_scale_workspace_bytes": (_z, [_i, _i]),
+    "dd_layer_norm_fwd_t": (_i, [_v, _ll, _i, _v, _v, _f, _v, _v, _v, _i, _v]),
+    "dd_layer_norm_bwd_t": (_i, [_v, _v, _v, _v, _v, _ll, _i, _v, _v, _v, _z, _i, _v]),
+    "dd_layer_scale_bwd_t": (_i, [_v, _v, _v, _i, _i, _i, _v, _v, _v, _z, _i, _v]),
+    "dd_layer_scale_fwd_t": (_i, [_v, _v, _v, _i, _i, _i, _v, _i, _v]),
+    "dd_dwconv3x3_nhwc_t": (_i, [_v, _v, _i, _i, _i, _i, _i, _v, _i, _v]),
+    "dd_dwconv3x3_nhwc_bwd_data_t": (_i, [_v, _v, _i, _i, _i, _i, _i, _v, _i, _v]),
+    "dd_dwconv3x3_nhwc_bwd_weight_t": (_i, [_v, _v, _i, _i, _i, _i, _i, _v, _v, _z, _i, _v]),
+    "dd_redu_supported": (_i, [_i, _i]),
+    "dd_redu_workspace_bytes": (_z, [_ll, _i, _i]),
+    "dd_redu_fwd": (_i, [_v, _v, _v, _v, _ll, _i, _i, _v, _v]),
+    "dd_redu_bwd_data": (_i, [_v, _v, _ll, _i, _i, _v, _v, _v]),
+    "dd_redu_bwd_weight": (_i, [_v, _v, _v, _ll, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_conv_head_supported": (_i, [_i]),
+    "dd_conv_head_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dd_conv_head_fwd": (_i, [_v, _v, _ll, _ll, _ll, _v, _i, _i, _i, _i, _v, _v]),
+    "dd_conv_head_bwd_weight": (_i, [_v, _v, _i, _i, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_conv_small_supported": (_i, [_i, _i, _i]),
+    "dd_conv_small_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_conv_small_fwd": (_i, [_v, _v, _ll, _ll, _ll, _ll, _v, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv_small_bwd_data": (_i, [_v, _v, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv_small_bwd_weight": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_conv3x3_mfma_supported": (_i, [_i, _i]),
+    "dd_conv3x3_mfma_pack_bytes": (_z, [_i, _i]),
+    "dd_conv3x3_mfma_pack": (_i, [_v, _ll, _ll, _ll, _ll, _i, _i, _v, _v, _v]),
+    "dd_conv3x3_mfma_pack_many_job_words": (_i, []),
+    "dd_conv3x3_mfma_pack_many_blocks": (_i, [_i, _i, _i, _i]),
+    "dd_conv3x3_mfma_pack_many": (_i, [_v, _v, _i, _v]),
+    "dd_conv3x3_mfma": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_conv3x3_mfma_n": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_conv3x3_mfma_flat_supported": (_i, [_i, _i, _i, _i, _i]),
+    "dd_conv3x3_mfma_flat_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dd_conv3x3_mfma_flat": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv3x3_mfma_flat_n": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv3x3_mfma_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dd_conv3x3_mfma_bwd_weight": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv3x3_mfma_bwd_weight_n": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_conv3x3_half_supported": (_i, [_i, _i]),
+    "dd_conv3x3_half_pack_bytes": (_z, [_i, _i]),
+    "dd_conv3x3_half_pack": (_i, [_v, _ll, _ll, _ll, _ll, _i, _i, _i, _v, _v, _v]),
+    "dd_conv3x3_half": (_i, [_v, _v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_conv3x3_half_wgrad_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dd_conv3x3_half_bwd_weight": (_i, [_v, _v, _i, _i, _i, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_pw_gemm_pack_bytes": (_z, [_i, _i]),
+    "dd_mlp_pack": (_i, [_v, _ll, _ll, _v, _ll, _ll, _i, _i, _v, _v, _v, _v, _v, _v]),
+    "dd_mlp_fwd_supported": (_i, [_i]),
+    "dd_mlp_fwd": (_i, [_v, _v, _v, _v, _v, _i, _i, _v, _v]),
+    "dd_mlp_fwd_splits": (_i, [_i, _i]),
+    "dd_mlp_fwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_mlp_fwd_n": (_i, [_v, _v, _v, _v, _v, _i, _i, _i, _i, _v, _v, _z, _v]),
+    "dd_pw_gemm": (_i, [_v, _v, _v, _i, _i, _i, _i, _v, _v]),
+    "dd_gelu_pair": (_i, [_v, _v, _v, _z, _v]),
+    "dd_mlp_train_pack": (_i, [_v, _ll, _ll, _v, _ll, _ll, _i, _i, _v, _v, _v, _v, _v]),
+    "dd_mlp_train_pack_narrow": (_i, [_v, _ll, _ll, _v, _ll, _ll, _i, _i, _v, _v, _v, _v, _v]),
+    "dd_mlp_train_fwd": (_i, [_v, _v, _v, _v, _v, _i, _i, _i, _i, _v, _v, _v, _v, _z, _v]),
+    "dd_mlp_train_bwd_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_mlp_train_bwd": (_i, [_v, _v, _v, _v, _i, _i, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_linear_wgrad_supported": (_i, [_i, _i, _i]),
+    "dd_linear_wgrad_workspace_bytes": (_z, [_i, _i, _i]),
+    "dd_linear_wgrad": (_i, [_v, _v, _i, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_linear_wgrad_n": (_i, [_v, _v, _i, _i, _i, _i, _v, _v, _v, _z, _v]),
+    "dd_adam_chunk": (_i, []),
+    "dd_adam_multi": (_i, [_v, _i, _v, _i, _v, _d, _d, _d, _d, _d, _v, _v, _v]),
+    "dd_error_string": (C.c_char_p, [_i]),
+    "dd_abi_version": (_i, []),
+}
+EXPORTED = tuple(SIGNATURES)
+
+
 def declare(lib):
-    """Attach argtypes/restypes for every entry point of include/dynamo_hip.h."""
-    i, f, v, z = C.c_int, C.c_float, C.c_void_p, C.c_size_t
-    sig = {
-        "dd_photo_loss": (i, [C.POINTER(DDPhotoArgs), v]),
-        "dd_photo_workspace_bytes": (z, [C.POINTER(DDPhotoArgs)]),
-        "dd_photo_timing": (i, [i]),
-        "dd_photo_timing_read": (i, [C.POINTER(C.c_float), C.POINTER(i), i]),
-        "dd_smooth_loss": (i, [v, v, i, i, i, i, i, f, v, v, v, v]),
-        "dd_smooth_workspace_bytes": (z, [i, i, i, i]),
-        "dd_ground_loss": (i, [v, v, v, i, i, i, i, i, f, f, f, f, f, v, v, v, v, v]),
-        "dd_ground_workspace_bytes": (z, [i, i, i, i]),
-        "dd_resize_workspace_bytes": (z, [i, i, i, i, i]),
-        "dd_resize_bicubic": (i, [v, i, i, i, v, v, i, i, v, v, i, v, v, i, v, z, v]),
-        "dd_ground_candidates": (i, [v, v, v, i, i, i, i, i, f, f, f, v, v]),
-        "dd_ground_select": (i, [v, v, v, i, i, i, i, f, f, f, f, f, v, v, v, v, v, v]),
-        "dd_ground_plane": (i, [v, v, i, i, i, i, i, f, f, v, v, v, v]),
-        "dd_assemble_losses": (i, [v, C.POINTER(DDAssembleArgs), v, v, v]),
-        "dd_reg_losses_finish": (i, [C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v]),
-        "dd_fused_loss": (i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v]),
-        "dd_fused_loss_part": (i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs), C.POINTER(DDAssembleArgs), v, v, v, i]),
-        "dd_fused_loss_supported": (i, [C.POINTER(DDPhotoArgs), C.POINTER(DDRegArgs)]),
-        "dd_reg_workspace_bytes": (z, [C.POINTER(DDRegArgs)]),
-        "dd_jpeg_workspace_bytes": (z, [i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "dd_jpeg_decode": (i, [v, C.c_longlong, v, i, i, i, i, C.POINTER(C.c_int), C.POINTER(C.c_int), v, v, z, v]),
-        "dd_backproject": (i, [v, v, i, i, i, v, v]),
-        "dd_backproject_bwd": (i, [v, v, i, i, i, v, v]),
-        "dd_project3d": (i, [v, v, v, i, i, i, f, v, v, v]),
-        "dd_project3d_bwd": (i, [v, v, v, v, v, i, i, i, f, v, v, v, v]),
-        "dd_project3d_workspace_bytes": (z, [i, i, i]),
-        "dd_ssim": (i, [v, v, i, i, i, i, v, v]),
-        "dd_ssim_bwd": (i, [v, v, v, i, i, i, i, v, v, v]),
-        "dd_disp_to_depth": (i, [v, z, f, f, v, v, v]),
-        "dd_pose_matrix": (i, [v, v, i, i, v, v]),
-        "dd_pose_matrix_bwd": (i, [v, v, v, i, i, v, v, v]),
-        "dd_channel_sum_nhwc": (i, [v, C.c_longlong, i, v, v, v]),
-        "dd_channel_sum_workspace_bytes": (z, [i]),
-        "dd_reflect_pad1_nhwc": (i, [v, i, i, i, i, v, v]),
-        "dd_reflect_pad1_nhwc_bwd": (i, [v, i, i, i, i, v, v]),
-        "dd_dwconv3x3_nhwc": (i, [v, v, i, i, i, i, i, v, v]),
-        "dd_dwconv3x3_nhwc_bwd_data": (i, [v, v, i, i, i, i, i, v, v]),
-        "dd_dwconv3x3_nhwc_bwd_weight": (i, [v, v, i, i, i, i, i, v, v, z, v]),
-        "dd_dwconv3x3_workspace_bytes": (z, [i, i, i]),
-        "dd_conv3x3_cout1_bwd_data": (i, [v, v, i, i, i, i, i, v, v]),
-        "dd_prepare_frames": (i, [v, v, v, i, i, i, i, v, v, v, v]),
-        "dd_prepare_frames_workspace_bytes": (z, [i, i]),
-        "dd_pyramid_down2": (i, [v, i, i, i, v, v]),
-        "dd_pack_rgb": (i, [v, i, i, i, v, v]),
-        "dd_depth_metrics": (i, [v, i, i, i, v, v, i, v, C.POINTER(C.c_double), f, f, v, v, v, z, v]),
-        "dd_depth_metrics_workspace_bytes": (z, [i, i]),
-        "dd_depth_metrics_masked": (i, [v, i, i, i, v, v, i, v, C.POINTER(C.c_double), f, f, v, i, i, v, v, v, v, z, v]),
-        "dd_depth_metrics_masked_workspace_bytes": (z, [i, i]),
-        "dd_depth_metrics_accumulate": (i, [v, v, i, v, v, v]),
-        "dd_odom_snippet_count": (i, [i, i]),
-        "dd_odom_snippets": (i, [v, v, i, i, v, v, v]),
-        "dd_motion_pr": (i, [v, i, i, i, v, v, i, i, v, i, i, v, v]),
-        "dd_fill_contours": (i, [v, i, v, i, i, i, i, v, v]),
-        "dd_lidar_depth_points_workspace_bytes": (z, [i, i, i, i]),
-        "dd_lidar_depth_points": (i, [v, C.c_longlong, C.POINTER(C.c_int32), i, v, i, i, i, v, v, v, v, z, v]),
-        "dd_lidar_pose_points_workspace_bytes": (z, [i, C.c_longlong]),
-        "dd_lidar_pose_points": (i, [v, C.c_longlong, C.POINTER(C.c_int32), i, v, v, v, v, z, v]),
-        "dd_box_fit": (i, [v, i, v, v, i, v, v, i, v, v, v]),
-        "dd_resize_area": (i, [v, i, i, i, v, i, i, v, v, v, i, v, v, v, i, v]),
-        "dd_vis_frame": (i, [v, v, v, v, v, v, v, v, f, f, i, i, C.POINTER(C.c_int), i, i, i, v, f, f, f, f, i, i, v, v, v, v]),
-        "dd_vis_flow_tiles": (i, [v, v, C.POINTER(C.c_int), i, i, i, i, i, i, f, i, v, v]),
-        "dd_export_depth": (i, [v, v, v, i, i, i, i, i, f, f, f, v, f, f, v, v, v, v]),
-        "dd_export_plane_u8": (i, [v, i, i, i, i, i, v, v]),
-        "dd_export_cloud_workspace_bytes": (z, [i, i, i, i]),
-        "dd_export_cloud": (i, [v, v, v, v, v, v, i, i, i, i, i, f, f, f, f, f, f, f, f, f, i, v, v, v, z, v]),
-        "dd_objects_workspace_bytes": (z, [i, i, i, i]),
-        "dd_objects": (i, [v, v, v, v, v, v, v, i, i, i, f, f, f, f, f, f, f, i, i, i, v, v, v, v, z, v]),
-        "dd_export_labels_u16": (i, [v, i, i, i, i, i, v, v]),
-        "dd_bn_act_fwd": (i, [v, v, C.c_longlong, i, v, v, f, f, v, v, v, v, i, v, v, z, v]),
-        "dd_bn_act_bwd": (i, [v, v, v, C.c_longlong, i, v, v, v, v, i, v, v, v, v, v, z, v]),
-        "dd_bn_workspace_bytes": (z, [i]),
-        "dd_bn_act_fwd_t": (i, [v, v, C.c_longlong, i, v, v, f, f, v, v, v, v, i, v, i, v, z, v]),
-        "dd_bn_act_bwd_t": (i, [v, v, v, C.c_longlong, i, v, v, v, v, i, v, v, v, v, i, v, z, v]),
-        "dd_channel_sum_nhwc_t": (i, [v, C.c_longlong, i, v, i, v, v]),
-        "dd_reflect_pad1_nhwc_t": (i, [v, i, i, i, i, v, i, v]),
-        "dd_reflect_pad1_nhwc_bwd_t": (i, [v, i, i, i, i, v, i, v]),
-        "dd_up_cat_pad_t": (i, [v, v, i, i, i, i, i, i, i, v, i, v]),
-        "dd_up_cat_pad_bwd_t": (i, [v, v, i, i, i, i, i, i, i, v, v, i, v]),
-        "dd_layer_norm_fwd": (i, [v, C.c_longlong, i, v, v, f, v, v, v, v]),
-        "dd_layer_norm_bwd": (i, [v, v, v, v, v, C.c_longlong, i, v, v, v, z, v]),
-        "dd_layer_norm_workspace_bytes": (z, [i]),
-        "dd_layer_scale_bwd": (i, [v, v, v, i, i, i, v, v, v, z, v]),
-        "dd_layer_scale_workspace_bytes": (z, [i, i]),
-        "dd_layer_norm_fwd_t": (i, [v, C.c_longlong, i, v, v, f, v, v, v, i, v]),
-        "dd_layer_norm_bwd_t": (i, [v, v, v, v, v, C.c_longlong, i, v, v, v, z, i, v]),
-        "dd_layer_scale_bwd_t": (i, [v, v, v, i, i, i, v, v, v, z, i, v]),
-        "dd_layer_scale_fwd_t": (i, [v, v, v, i, i, i, v, i, v]),
-        "dd_dwconv3x3_nhwc_t": (i, [v, v, i, i, i, i, i, v, i, v]),
-        "dd_dwconv3x3_nhwc_bwd_data_t": (i, [v, v, i, i, i, i, i, v, i, v]),
-        "dd_dwconv3x3_nhwc_bwd_weight_t": (i, [v, v, i, i, i, i, i, v, v, z, i, v]),
-        "dd_redu_supported": (i, [i, i]),
-        "dd_redu_workspace_bytes": (z, [C.c_longlong, i, i]),
-        "dd_redu_fwd": (i, [v, v, v, v, C.c_longlong, i, i, v, v]),
-        "dd_redu_bwd_data": (i, [v, v, C.c_longlong, i, i, v, v, v]),
-        "dd_redu_bwd_weight": (i, [v, v, v, C.c_longlong, i, i, v, v, v, z, v]),
-        "dd_conv_head_supported": (i, [i]),
-        "dd_conv_head_workspace_bytes": (z, [i, i, i, i]),
-        "dd_conv_head_fwd": (i, [v, v, C.c_longlong, C.c_longlong, C.c_longlong, v, i, i, i, i, v, v]),
-        "dd_conv_head_bwd_weight": (i, [v, v, i, i, i, i, v, v, v, z, v]),
-        "dd_conv_small_supported": (i, [i, i, i]),
-        "dd_conv_small_workspace_bytes": (z, [i, i, i]),
-        "dd_conv_small_fwd": (i, [v, v, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, v, i, i, i, i, i, i, v, v, z, v]),
-        "dd_conv_small_bwd_data": (i, [v, v, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, i, i, i, i, i, i, v, v, z, v]),
-        "dd_conv_small_bwd_weight": (i, [v, v, i, i, i, i, i, i, v, v, v, z, v]),
-        "dd_conv3x3_mfma_supported": (i, [i, i]),
-        "dd_conv3x3_mfma_pack_bytes": (z, [i, i]),
-        "dd_conv3x3_mfma_pack": (i, [v, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, i, i, v, v, v]),
-        "dd_conv3x3_mfma_pack_many_job_words": (i, []),
-        "dd_conv3x3_mfma_pack_many_blocks": (i, [i, i, i, i]),
-        "dd_conv3x3_mfma_pack_many": (i, [v, v, i, v]),
-        "dd_conv3x3_mfma": (i, [v, v, v, i, i, i, i, i, i, v, v]),
-        "dd_conv3x3_mfma_n": (i, [v, v, v, i, i, i, i, i, i, i, v, v]),
-        "dd_conv3x3_mfma_flat_supported": (i, [i, i, i, i, i]),
-        "dd_conv3x3_mfma_flat_workspace_bytes": (z, [i, i, i, i, i]),
-        "dd_conv3x3_mfma_flat": (i, [v, v, v, i, i, i, i, i, v, v, z, v]),
-        "dd_conv3x3_mfma_flat_n": (i, [v, v, v, i, i, i, i, i, i, v, v, z, v]),
-        "dd_conv3x3_mfma_wgrad_workspace_bytes": (z, [i, i, i, i, i]),
-        "dd_conv3x3_mfma_bwd_weight": (i, [v, v, i, i, i, i, i, i, v, v, z, v]),
-        "dd_conv3x3_mfma_bwd_weight_n": (i, [v, v, i, i, i, i, i, i, i, v, v, z, v]),
-        "dd_conv3x3_half_supported": (i, [i, i]),
-        "dd_conv3x3_half_pack_bytes": (z, [i, i]),
-        "dd_conv3x3_half_pack": (i, [v, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, i, i, i, v, v, v]),
-        "dd_conv3x3_half": (i, [v, v, v, i, i, i, i, i, i, i, v, v]),
-        "dd_conv3x3_half_wgrad_workspace_bytes": (z, [i, i, i, i, i]),
-        "dd_conv3x3_half_bwd_weight": (i, [v, v, i, i, i, i, i, i, i, v, v, z, v]),
-        "dd_pw_gemm_pack_bytes": (z, [i, i]),
-        "dd_mlp_pack": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v, v]),
-        "dd_mlp_fwd_supported": (i, [i]),
-        "dd_mlp_fwd": (i, [v, v, v, v, v, i, i, v, v]),
-        "dd_mlp_fwd_splits": (i, [i, i]),
-        "dd_mlp_fwd_workspace_bytes": (z, [i, i, i]),
-        "dd_mlp_fwd_n": (i, [v, v, v, v, v, i, i, i, i, v, v, z, v]),
-        "dd_pw_gemm": (i, [v, v, v, i, i, i, i, v, v]),
-        "dd_gelu_pair": (i, [v, v, v, z, v]),
-        "dd_mlp_train_pack": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v]),
-        "dd_mlp_train_pack_narrow": (i, [v, C.c_longlong, C.c_longlong, v, C.c_longlong, C.c_longlong, i, i, v, v, v, v, v]),
-        "dd_mlp_train_fwd": (i, [v, v, v, v, v, i, i, i, i, v, v, v, v, z, v]),
-        "dd_mlp_train_bwd_workspace_bytes": (z, [i, i, i]),
-        "dd_mlp_train_bwd": (i, [v, v, v, v, i, i, i, i, v, v, v, z, v]),
-        "dd_linear_wgrad_supported": (i, [i, i, i]),
-        "dd_linear_wgrad_workspace_bytes": (z, [i, i, i]),
-        "dd_linear_wgrad": (i, [v, v, i, i, i, v, v, v, z, v]),
-        "dd_linear_wgrad_n": (i, [v, v, i, i, i, i, v, v, v, z, v]),
-        "dd_adam_chunk": (i, []),
-        "dd_adam_multi": (i, [v, i, v, i, v, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, v, v, v]),
-        "dd_error_string": (C.c_char_p, [i]),
-        "dd_abi_version": (i, []),
-    }
-    found = []
-    for name, (res, args) in sig.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError:
+    """Attaches restype/argtypes for every entry point of include/dynamo_hip.h and returns their names.  A library that lacks some
+    of them (a stale build) gets the others set, then an AttributeError that names every missing one."""
+    missing = []
+    for name, (res, args) in SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            missing.append(name)
             continue
         fn.restype = res
         fn.argtypes = args
-        found.append(name)
-    return found
-
-
-EXPORTED = (
-    "dd_photo_loss", "dd_photo_workspace_bytes", "dd_photo_timing", "dd_photo_timing_read", "dd_photo_loss_part", "dd_smooth_loss", "dd_smooth_workspace_bytes",
-    "dd_ground_loss", "dd_ground_workspace_bytes", "dd_ground_plane", "dd_ground_candidates", "dd_ground_select",
-    "dd_assemble_losses", "dd_reg_losses_finish", "dd_fused_loss", "dd_fused_loss_part", "dd_fused_loss_supported", "dd_reg_workspace_bytes", "dd_backproject", "dd_backproject_bwd", "dd_project3d", "dd_project3d_bwd", "dd_project3d_workspace_bytes",
-    "dd_ssim", "dd_ssim_bwd", "dd_disp_to_depth", "dd_pose_matrix", "dd_pose_matrix_bwd",
-    "dd_channel_sum_nhwc", "dd_channel_sum_workspace_bytes", "dd_reflect_pad1_nhwc", "dd_reflect_pad1_nhwc_bwd",
-    "dd_dwconv3x3_nhwc", "dd_dwconv3x3_nhwc_bwd_data", "dd_dwconv3x3_nhwc_bwd_weight", "dd_dwconv3x3_workspace_bytes", "dd_conv3x3_cout1_bwd_data",
-    "dd_prepare_frames", "dd_prepare_frames_workspace_bytes", "dd_pyramid_down2", "dd_pack_rgb", "dd_depth_metrics", "dd_depth_metrics_workspace_bytes", "dd_depth_metrics_masked", "dd_depth_metrics_masked_workspace_bytes", "dd_depth_metrics_accumulate", "dd_odom_snippet_count", "dd_odom_snippets", "dd_motion_pr", "dd_fill_contours", "dd_lidar_depth_points", "dd_lidar_depth_points_workspace_bytes", "dd_lidar_pose_points", "dd_lidar_pose_points_workspace_bytes", "dd_box_fit", "dd_resize_area", "dd_vis_frame", "dd_vis_flow_tiles", "dd_export_depth", "dd_export_plane_u8", "dd_export_cloud_workspace_bytes", "dd_export_cloud", "dd_objects_workspace_bytes", "dd_objects", "dd_export_labels_u16", "dd_bn_act_fwd", "dd_bn_act_bwd", "dd_bn_workspace_bytes",
-    "dd_bn_act_fwd_t", "dd_bn_act_bwd_t", "dd_channel_sum_nhwc_t", "dd_reflect_pad1_nhwc_t", "dd_reflect_pad1_nhwc_bwd_t", "dd_up_cat_pad_t", "dd_up_cat_pad_bwd_t",
-    "dd_layer_norm_fwd", "dd_layer_norm_bwd", "dd_layer_norm_workspace_bytes", "dd_layer_scale_bwd", "dd_layer_scale_workspace_bytes",
-    "dd_jpeg_workspace_bytes", "dd_jpeg_decode", "dd_resize_workspace_bytes", "dd_resize_bicubic", "dd_layer_norm_fwd_t", "dd_layer_norm_bwd_t", "dd_layer_scale_bwd_t", "dd_layer_scale_fwd_t", "dd_dwconv3x3_nhwc_t", "dd_dwconv3x3_nhwc_bwd_data_t",
-    "dd_dwconv3x3_nhwc_bwd_weight_t", "dd_adam_chunk", "dd_adam_multi", "dd_conv_small_supported", "dd_conv_small_workspace_bytes",
-    "dd_conv_small_fwd", "dd_conv_small_bwd_data", "dd_conv_small_bwd_weight", "dd_conv_head_supported", "dd_conv_head_workspace_bytes", "dd_conv_head_fwd",
-    "dd_conv_head_bwd_weight", "dd_redu_supported", "dd_redu_workspace_bytes", "dd_redu_fwd", "dd_redu_bwd_data", "dd_redu_bwd_weight",
-    "dd_conv3x3_mfma_supported", "dd_conv3x3_mfma_pack_bytes", "dd_conv3x3_mfma_pack", "dd_conv3x3_mfma_pack_many_job_words",
-    "dd_conv3x3_mfma_pack_many_blocks", "dd_conv3x3_mfma_pack_many", "dd_conv3x3_mfma", "dd_conv3x3_mfma_n",
-    "dd_conv3x3_mfma_flat_supported", "dd_conv3x3_mfma_flat_workspace_bytes", "dd_conv3x3_mfma_flat", "dd_conv3x3_mfma_flat_n",
-    "dd_conv3x3_mfma_wgrad_workspace_bytes", "dd_conv3x3_mfma_bwd_weight", "dd_conv3x3_mfma_bwd_weight_n",
-    "dd_conv3x3_half_supported", "dd_conv3x3_half_pack_bytes", "dd_conv3x3_half_pack", "dd_conv3x3_half",
-    "dd_conv3x3_half_wgrad_workspace_bytes", "dd_conv3x3_half_bwd_weight",
-    "dd_pw_gemm_pack_bytes", "dd_mlp_pack", "dd_pw_gemm", "dd_gelu_pair", "dd_mlp_fwd_supported", "dd_mlp_fwd", "dd_mlp_fwd_splits", "dd_mlp_fwd_workspace_bytes", "dd_mlp_fwd_n",
-    "dd_mlp_train_pack", "dd_mlp_train_pack_narrow", "dd_mlp_train_fwd", "dd_mlp_train_bwd_workspace_bytes", "dd_mlp_train_bwd",
-    "dd_linear_wgrad_supported", "dd_linear_wgrad_workspace_bytes", "dd_linear_wgrad", "dd_linear_wgrad_n",
-    "dd_error_string", "dd_abi_version",
-)
+    if missing:
+        raise AttributeError("no symbol " + ", ".join(missing))
+    return EXPORTED
 
 
 def fill_photo_args(*, B, H, W, mode, automask, want_grad, min_depth, max_depth, ssim_weight, eps, disp_thr,

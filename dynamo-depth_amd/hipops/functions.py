@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from . import lib as L
+from . import abi, lib as L
 from .pack_many import PackSet, _ACTIVE_PACK_SETS, _pack_many_on, pack_many_launches, pack_weights_once_per_forward  # noqa: F401 (re-exported)
 
 
@@ -25,7 +25,7 @@ def _dev(t, name="tensor"):
 
 
 # element-type codes of the *_t entry points (include/dynamo_hip.h): the tensors of an autocast forward keep their own type
-DTYPE_CODE = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
+DTYPE_CODE = {torch.float32: abi.DD_DTYPE_F32, torch.float16: abi.DD_DTYPE_F16, torch.bfloat16: abi.DD_DTYPE_BF16}
 
 
 def _p(t):
@@ -284,7 +284,7 @@ class SmoothLossFn(torch.autograd.Function):
 
 
 class ConvBiasFn(torch.autograd.Function):
-    """conv2d with bias whose BIAS gradient is computed by dd_channel_sum_nhwc when the output gradient is channels-last.
+    """conv2d with bias whose BIAS gradient is computed by dd_channel_sum_nhwc_t when the output gradient is channels-last.
     ATen computes it with a generic reduction that takes 1.9 ms for one full-resolution 9-channel conv of the motion decoders
     (4 such convs per step); everything else (forward, input / weight gradients) stays MIOpen via the aten ops."""
 
@@ -587,7 +587,7 @@ class MfmaConvFn(torch.autograd.Function):
     """conv2d 3x3 stride 1 (+ bias) through dd_conv3x3_mfma (csrc/dd_conv_mfma.hip): the motion decoders' refinement convolutions
     (reference networks/motion_decoder.py:24-33,57-66).  Forward and data gradient run on the bf16 matrix pipe with every fp32 operand split
     exactly into three bf16 pieces (fp32 accuracy), and so does the weight gradient (pixels as the contraction, per-workgroup partials folded
-    in a fixed order); the bias gradient is dd_channel_sum_nhwc.  Every result is bit-reproducible."""
+    in a fixed order); the bias gradient is dd_channel_sum_nhwc_t.  Every result is bit-reproducible."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, pad):
@@ -699,7 +699,7 @@ class HalfConvFn(torch.autograd.Function):
     """conv2d 3x3 stride 1 (+ bias) of a half-precision network through dd_conv3x3_half (csrc/dd_conv_half.hip): forward and data gradient on
     the half-precision matrix pipe with fp32 accumulation, the fp32 master weight converted while it is packed (no cast launch), the
     weight gradient likewise with an fp32 result (32+ channels on both sides; below that the library's half-precision kernel, its result
-    promoted to the master weight's fp32 as autocast's own backward does), the bias gradient through dd_channel_sum_nhwc.  BASELINE.json config 5 ("fp16 (CDNA4 MFMA conv)")."""
+    promoted to the master weight's fp32 as autocast's own backward does), the bias gradient through dd_channel_sum_nhwc_t.  BASELINE.json config 5 ("fp16 (CDNA4 MFMA conv)")."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, pad):

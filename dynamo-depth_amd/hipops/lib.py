@@ -39,7 +39,10 @@ def load():
                 "libdynamo_hip.so not found at %s -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback for the loss path)" % LIB_PATH)
         lib = C.CDLL(LIB_PATH)
-        abi.declare(lib)
+        try:
+            abi.declare(lib)
+        except AttributeError as e:
+            raise DynamoHipError("%s is stale (%s) -- rebuild it with `python -c 'import __graft_entry__ as g; g.build()'`" % (LIB_PATH, e))
         if lib.dd_abi_version() != abi.DD_ABI_VERSION:
             raise DynamoHipError("ABI mismatch between hipops/abi.py and libdynamo_hip.so")
         _lib = lib

@@ -325,28 +325,36 @@ int dd_pose_matrix(const float* axisangle, const float* translation, int B, int 
 int dd_pose_matrix_bwd(const float* axisangle, const float* translation, const float* g_T, int B, int invert,
                        float* g_axisangle, float* g_translation, void* stream);
 
+/* Element-typed entry points (the `_t` suffix): `dtype` selects the type of the activation / gradient tensors passed as void* --
+ * DD_DTYPE_F32, DD_DTYPE_F16, DD_DTYPE_BF16; the last two are the tensors of an autocast forward (config "fp16 convs" of BASELINE.json,
+ * config 5 with the LiteMono depth net) -- read and written four elements at a time (half types move 8 bytes per access).  Statistics,
+ * affine parameters, convolution weights (the fp32 master copies), sums and every intermediate stay fp32. */
+#define DD_DTYPE_F32 0
+#define DD_DTYPE_F16 1
+#define DD_DTYPE_BF16 2
+
 /* Bias gradient of a convolution whose output gradient is channels-last: out[c] = sum over rows of x[row*C + c]
- * (x = (B,H,W,C) memory, rows = B*H*W).  Replaces ATen's generic reduction, which is ~100x off the HBM roofline for
+ * (x = (B,H,W,C) memory of type `dtype`, rows = B*H*W; out fp32).  Replaces ATen's generic reduction, which is ~100x off the HBM roofline for
  * small C (the full-resolution 9-channel convs of networks/motion_decoder.py); any C >= 1 (C > 256, the bias gradients of
  * LiteMono's point-wise Linears -- networks/depth_encoder.py:200-203 --, takes a column-per-thread kernel).
  * workspace: dd_channel_sum_workspace_bytes(C). */
-int dd_channel_sum_nhwc(const float* x, long long rows, int C, float* out, float* workspace, void* stream);
+int dd_channel_sum_nhwc_t(const void* x, long long rows, int C, float* out, int dtype, float* workspace, void* stream);
 size_t dd_channel_sum_workspace_bytes(int C);
 
 /* nn.ReflectionPad2d(1) of networks.layers.Conv3x3 (reference networks/layers.py:100-115) for channels-last tensors:
  * x (B,H,W,C) memory -> out (B,H+2,W+2,C); *_bwd is its adjoint (g_out (B,H+2,W+2,C) -> g_x (B,H,W,C), overwritten). */
-int dd_reflect_pad1_nhwc(const float* x, int B, int H, int W, int C, float* out, void* stream);
-int dd_reflect_pad1_nhwc_bwd(const float* g_out, int B, int H, int W, int C, float* g_x, void* stream);
+int dd_reflect_pad1_nhwc_t(const void* x, int B, int H, int W, int C, void* out, int dtype, void* stream);
+int dd_reflect_pad1_nhwc_bwd_t(const void* g_out, int B, int H, int W, int C, void* g_x, int dtype, void* stream);
 
 /* Depth-wise (groups == channels) 3x3 convolution, stride 1, zero padding == dilation, no bias, on channels-last tensors:
  * LiteMono's CDilated inside DilatedConv (reference networks/depth_encoder.py:168-181, 197-199 -- nn.Conv2d(dim, dim, 3,
- * padding=d, dilation=d, groups=dim, bias=False)). x, out, g_*: [B,H,W,C] floats (the memory of a channels_last NCHW tensor),
- * weight/g_weight: [C,1,3,3] contiguous; C a multiple of 4, <= 512. The weight gradient is a fixed-order two-level sum
+ * padding=d, dilation=d, groups=dim, bias=False)). x, out, g_*: [B,H,W,C] elements of type `dtype` (the memory of a channels_last NCHW
+ * tensor), weight/g_weight: [C,1,3,3] contiguous fp32; C a multiple of 4, <= 512. The weight gradient is a fixed-order two-level sum
  * (one record per image row in `workspace`, dd_dwconv3x3_workspace_bytes(B,H,C) bytes), so it is run-to-run reproducible. */
-int dd_dwconv3x3_nhwc(const float* x, const float* weight, int B, int H, int W, int C, int dilation, float* out, void* stream);
-int dd_dwconv3x3_nhwc_bwd_data(const float* g_out, const float* weight, int B, int H, int W, int C, int dilation, float* g_x, void* stream);
-int dd_dwconv3x3_nhwc_bwd_weight(const float* g_out, const float* x, int B, int H, int W, int C, int dilation, float* g_weight,
-                                 void* workspace, size_t workspace_bytes, void* stream);
+int dd_dwconv3x3_nhwc_t(const void* x, const float* weight, int B, int H, int W, int C, int dilation, void* out, int dtype, void* stream);
+int dd_dwconv3x3_nhwc_bwd_data_t(const void* g_out, const float* weight, int B, int H, int W, int C, int dilation, void* g_x, int dtype, void* stream);
+int dd_dwconv3x3_nhwc_bwd_weight_t(const void* g_out, const void* x, int B, int H, int W, int C, int dilation, float* g_weight, void* workspace,
+                                   size_t workspace_bytes, int dtype, void* stream);
 size_t dd_dwconv3x3_workspace_bytes(int B, int H, int C);
 
 /* Data gradient of a 3x3, stride-1 convolution with ONE output channel (the disparity heads: networks/depth_decoder.py:49-51,
@@ -501,35 +509,19 @@ int dd_box_fit(const double* points, int n_points, const int32_t* seg, const int
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
  * bn2(+identity)->relu as used by networks/resnet_encoder.py:42-88, the stem bn1->relu, and LiteMono's BNGELU / DilatedConv.bn1
- * (networks/depth_encoder.py:137-148,197-199).  x, residual, out, g_*: [rows, C] floats (rows = B*H*W of an NHWC tensor),
+ * (networks/depth_encoder.py:137-148,197-199).  x, residual, out, g_*: [rows, C] elements of type `dtype` (rows = B*H*W of an NHWC tensor),
  * C a multiple of 4, <= 512.  act: 0 none, 1 ReLU, 2 GELU (erf; not with a residual).  running_mean/var (may both be NULL) are
  * updated in place with `momentum` (unbiased variance, as PyTorch); save_mean/save_invstd [C] feed the backward.
  * Backward: g_x always; g_residual (NULL unless a residual was given and act != 0) = gradient after the activation;
  * `out` (backward): the ReLU mask is read from it when given -- REQUIRED when a residual was added in the forward; NULL for act == 1 without a residual: the mask is recomputed from x (the forward's own fmaf, the same bits), one read pass less.  Batch statistics: sum x and sum x^2 in fp64 from the first addition to the variance, fixed order (no cancellation at mean^2 in fp32).
  * workspace: dd_bn_workspace_bytes(C).  Two launches forward, two backward. */
-int dd_bn_act_fwd(const float* x, const float* residual, long long rows, int C, const float* gamma, const float* beta, float eps,
-                  float momentum, float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act,
-                  float* out, void* workspace, size_t workspace_bytes, void* stream);
-int dd_bn_act_bwd(const float* x, const float* g_out, const float* out, long long rows, int C, const float* gamma, const float* beta,
-                  const float* save_mean, const float* save_invstd, int act, float* g_x, float* g_residual, float* g_gamma,
-                  float* g_beta, void* workspace, size_t workspace_bytes, void* stream);
-size_t dd_bn_workspace_bytes(int C);
-
-/* Element-typed variants for the tensors of an autocast forward (config "fp16 convs" of BASELINE.json): `dtype` selects the type of
- * the activation / gradient tensors -- DD_DTYPE_F32, DD_DTYPE_F16, DD_DTYPE_BF16 -- read and written four elements at a time;
- * statistics, affine parameters, sums and every intermediate stay fp32.  The fp32 entry points above are dtype = 0 of these. */
-#define DD_DTYPE_F32 0
-#define DD_DTYPE_F16 1
-#define DD_DTYPE_BF16 2
 int dd_bn_act_fwd_t(const void* x, const void* residual, long long rows, int C, const float* gamma, const float* beta, float eps, float momentum,
                     float* running_mean, float* running_var, float* save_mean, float* save_invstd, int act, void* out, int dtype,
                     void* workspace, size_t workspace_bytes, void* stream);
 int dd_bn_act_bwd_t(const void* x, const void* g_out, const void* out, long long rows, int C, const float* gamma, const float* beta,
                     const float* save_mean, const float* save_invstd, int act, void* g_x, void* g_residual, float* g_gamma, float* g_beta,
                     int dtype, void* workspace, size_t workspace_bytes, void* stream);
-int dd_channel_sum_nhwc_t(const void* x, long long rows, int C, float* out, int dtype, float* workspace, void* stream);
-int dd_reflect_pad1_nhwc_t(const void* x, int B, int H, int W, int C, void* out, int dtype, void* stream);
-int dd_reflect_pad1_nhwc_bwd_t(const void* g_out, int B, int H, int W, int C, void* g_x, int dtype, void* stream);
+size_t dd_bn_workspace_bytes(int C);
 
 /* The glue between two 3x3 convolutions of the disparity decoders (reference networks/depth_decoder.py:40-53 Monodepth2,
  * :98-113 Lite-Mono; networks/layers.py:84-121) in one pass, channels-last:
@@ -546,40 +538,25 @@ int dd_up_cat_pad_bwd_t(const void* g_out, const void* x, int B, int h, int w, i
 
 /* LayerNorm over the last (channel) axis of a [rows, C] matrix -- LiteMono's LayerNorm(data_format="channels_last")
  * (networks/depth_encoder.py:101-128, used by LGFI at :241,:252): y = (x - mean) * rstd * gamma + beta, biased variance, eps
- * inside the square root.  C a multiple of 4, <= 256.  mean, rstd: [rows], kept for the backward.
+ * inside the square root.  x, y, g_out, g_x of type `dtype`; C a multiple of 4, <= 256.  mean, rstd: [rows] fp32, kept for the backward.
  * Backward: g_x [rows, C]; g_gamma_beta [2*C] = (d gamma, d beta), fixed-order column sums.  workspace:
  * dd_layer_norm_workspace_bytes(C).  One launch forward, two backward. */
-int dd_layer_norm_fwd(const float* x, long long rows, int C, const float* gamma, const float* beta, float eps, float* y, float* mean,
-                      float* rstd, void* stream);
-int dd_layer_norm_bwd(const float* x, const float* g_out, const float* gamma, const float* mean, const float* rstd, long long rows, int C,
-                      float* g_x, float* g_gamma_beta, void* workspace, size_t workspace_bytes, void* stream);
-size_t dd_layer_norm_workspace_bytes(int C);
-
-/* Backward of LiteMono's layer-scale residual out = res + y * scale[b,c] (scale = gamma x stochastic-depth factor; reference
- * networks/depth_encoder.py:219-226,266-274): g_y[b,r,c] = g_out[b,r,c] * scale[b,c] and g_scale[b,c] = sum_r g_out * y, one pass.
- * g_out, y, g_y: [B, rows, C] (rows = H*W of a channels-last image), scale, g_scale: [B, C]; C a multiple of 4, <= 1024.
- * workspace: dd_layer_scale_workspace_bytes(B, C).  The residual's own gradient is g_out itself. */
-int dd_layer_scale_bwd(const float* g_out, const float* y, const float* scale, int B, int rows, int C, float* g_y, float* g_scale,
-                       void* workspace, size_t workspace_bytes, void* stream);
-size_t dd_layer_scale_workspace_bytes(int B, int C);
-
-/* The same LiteMono hooks on the tensors of an autocast forward (BASELINE.json config 5 with the LiteMono depth net; round 3):
- * `dtype` is the storage type of the activations and their gradients (0 fp32, 1 fp16, 2 bf16, as for dd_bn_act_*_t); the
- * affine / convolution weights stay the fp32 master copies, statistics and every sum are fp32.  Half types move 8 bytes per
- * access (four channels). */
 int dd_layer_norm_fwd_t(const void* x, long long rows, int C, const float* gamma, const float* beta, float eps, void* y, float* mean, float* rstd,
                         int dtype, void* stream);
 int dd_layer_norm_bwd_t(const void* x, const void* g_out, const float* gamma, const float* mean, const float* rstd, long long rows, int C,
                         void* g_x, float* g_gamma_beta, void* workspace, size_t workspace_bytes, int dtype, void* stream);
+size_t dd_layer_norm_workspace_bytes(int C);
+
+/* Backward of LiteMono's layer-scale residual out = res + y * scale[b,c] (scale = gamma x stochastic-depth factor; reference
+ * networks/depth_encoder.py:219-226,266-274): g_y[b,r,c] = g_out[b,r,c] * scale[b,c] and g_scale[b,c] = sum_r g_out * y, one pass.
+ * g_out, y, g_y: [B, rows, C] of type `dtype` (rows = H*W of a channels-last image), scale, g_scale: [B, C] fp32; C a multiple of 4, <= 1024.
+ * workspace: dd_layer_scale_workspace_bytes(B, C).  The residual's own gradient is g_out itself. */
 int dd_layer_scale_bwd_t(const void* g_out, const void* y, const float* scale, int B, int rows, int C, void* g_y, float* g_scale, void* workspace,
                          size_t workspace_bytes, int dtype, void* stream);
+size_t dd_layer_scale_workspace_bytes(int B, int C);
 /* forward of the layer-scale residual, out = res + y * scale[b, c] (all (B,rows,C) channels-last, scale (B,C) fp32), evaluated in
  * fp32 whatever the storage type: the layer-scale parameters start at 1e-6, below fp16's normal range */
 int dd_layer_scale_fwd_t(const void* res, const void* y, const float* scale, int B, int rows, int C, void* out, int dtype, void* stream);
-int dd_dwconv3x3_nhwc_t(const void* x, const float* weight, int B, int H, int W, int C, int dilation, void* out, int dtype, void* stream);
-int dd_dwconv3x3_nhwc_bwd_data_t(const void* g_out, const float* weight, int B, int H, int W, int C, int dilation, void* g_x, int dtype, void* stream);
-int dd_dwconv3x3_nhwc_bwd_weight_t(const void* g_out, const void* x, int B, int H, int W, int C, int dilation, float* g_weight, void* workspace,
-                                   size_t workspace_bytes, int dtype, void* stream);
 
 /* The 1x1 reductions of the motion decoders as ONE operator (reference networks/motion_decoder.py:33,66: `refine_motion_redu{level}` =
  * Conv2d(2*ch, out_dim, 1) on cat(a, b)): y[p,co] = bias[co] + sum_c a[p,c] W[co,c] + sum_c b[p,c] W[co,C+c].

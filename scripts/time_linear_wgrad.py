@@ -1,4 +1,4 @@
-"""Weight + bias gradient of LiteMono's point-wise Linears per shape: the library path (MIOpen 1x1 weight gradient + dd_channel_sum_nhwc)
+"""Weight + bias gradient of LiteMono's point-wise Linears per shape: the library path (MIOpen 1x1 weight gradient + dd_channel_sum_nhwc_t)
 against dd_linear_wgrad (csrc/dd_linear_wgrad.hip).  One path per process, so that a kernel trace holds every launch of that path:
 
    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python scripts/time_linear_wgrad.py lib|own [reps]

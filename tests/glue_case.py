@@ -245,7 +245,7 @@ def x_half_is_a_copy(c):
     return c.mode != 1 and not c.elu
 
 
-# ---- dd_reflect_pad1_nhwc ----------------------------------------------------------------------------------------------------------
+# ---- dd_reflect_pad1_nhwc_t --------------------------------------------------------------------------------------------------------
 PAD_B = 2
 PAD_CASES = [(H, W, C) for (H, W) in ((4, 4), (4, 7), (9, 4)) for C in (1, 2, 3, 17)] + [(4, 255, 1)]      # the last: (W + 2) * C = 257
 

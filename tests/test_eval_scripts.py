@@ -76,10 +76,9 @@ def _count_functions():
     from tools import OdometryMetrics
     fns.append(lambda n, t: OdometryMetrics(t).snippet_count(n) if 2 <= t <= 16 else -1)
     try:
-        from hipops import lib
+        from hipops import abi, lib
         so = ctypes.CDLL(lib.LIB_PATH)
-        so.dd_odom_snippet_count.restype = ctypes.c_int
-        so.dd_odom_snippet_count.argtypes = [ctypes.c_int, ctypes.c_int]
+        abi.declare(so)
         fns.append(so.dd_odom_snippet_count)
     except (OSError, AttributeError):
         pass                        # the library does not load without a GPU runtime here: the pure-Python twins stand in

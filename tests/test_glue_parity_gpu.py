@@ -89,11 +89,11 @@ def test_up_cat_pad_refuses_same_size_below_four_columns(w):
     """mode 2 with w < 4: hipErrorInvalidValue from both entry points and an untouched output (at W = 3 column 1 is mirrored by both
     padded borders; F.pad's column multiplicities are 1, 3, 1 and pad_fold has one mirror slot).  Nothing is launched."""
     from hipops import lib as L
-    from hipops.functions import _p
+    from hipops.functions import DTYPE_CODE, _p
     lib = L.load()
     B, h, C1, C2 = 2, 4, 8, 4
     for dtype in GC.DTYPES:
-        code = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}[dtype]
+        code = DTYPE_CODE[dtype]
         x = torch.randn(B, h, w, C1, device="cuda").to(dtype)
         skip = torch.randn(B, h, w, C2, device="cuda").to(dtype)
         g = torch.randn(B, h + 2, w + 2, C1 + C2, device="cuda").to(dtype)
@@ -108,7 +108,7 @@ def test_up_cat_pad_refuses_same_size_below_four_columns(w):
         assert bool((gx == 7.0).all()) and bool((gs == 7.0).all())
 
 
-# ---- dd_reflect_pad1_nhwc ----------------------------------------------------------------------------------------------------------
+# ---- dd_reflect_pad1_nhwc_t --------------------------------------------------------------------------------------------------------
 @gpu
 @pytest.mark.parametrize("dtype", GC.DTYPES, ids=GC.dtype_name)
 @pytest.mark.parametrize("shape", GC.PAD_CASES, ids=str)

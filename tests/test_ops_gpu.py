@@ -100,7 +100,7 @@ def test_backward_matches_oracle_autograd(z):
 
 @pytest.mark.parametrize("shape", [(12, 9, 192, 640), (2, 1, 7, 5), (3, 256, 6, 20), (4, 33, 16, 16)])
 def test_conv_bias_gradient_channel_sum(shape):
-    """networks.layers.Conv2d (bias gradient through dd_channel_sum_nhwc) == nn.Conv2d, channels-last and contiguous."""
+    """networks.layers.Conv2d (bias gradient through dd_channel_sum_nhwc_t) == nn.Conv2d, channels-last and contiguous."""
     import torch.nn as nn
     from networks.layers import Conv2d
     B, C, H, W = shape

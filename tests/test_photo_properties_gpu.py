@@ -118,3 +118,33 @@ def test_batch_items_are_independent():
     launch(case2, args2)
     for a, b in zip(full, grads_of(t2)):
         assert torch.equal(a[perm.to(a.device)], b)
+
+
+@pytest.mark.parametrize("phase", ["disp_init", "fine_tune"])
+def test_part_calls_equal_the_whole_call(phase):
+    """dd_photo_loss_part 1 then 2 (the tile kernel, then combine + finalize: the TILE_CUT branch of the split pipeline) issues the
+    launches of dd_photo_loss in the same order: sums and gradients are equal bit for bit.  4 x 3 tiles, every scale shift; the rigid
+    case with automask and the flow-plus-mask case.  part = 3 is refused before anything is launched."""
+    from hipops import lib as L
+    case = make_case(phase, 2, 64, 96, [0, 1, 2, 3], seed=7)                 # = pc.Case(phase, 2, 64, 96, [0, 1, 2, 3]) with its outputs
+    args, t = case.photo_buffers("cuda", materialise=False, want_grad=True)
+    launch(case, args)
+    ref, sums = grads_of(t), t["sums"].clone()
+    assert all(torch.isfinite(g).all() for g in ref) and sum(float(g.abs().sum()) for g in ref) > 0
+    for g in t["g_T"]:
+        g.zero_()
+    for d in t["scales"]:
+        d["g_disp"].zero_()
+        for key in ("g_flow", "g_mask"):
+            for g in d.get(key, []):
+                g.zero_()
+    t["sums"].zero_()
+    lib = L.load()
+    for part in (1, 2):
+        L.check(lib.dd_photo_loss_part(C.byref(args), L.current_stream(), part), "dd_photo_loss_part %d" % part)
+    torch.cuda.synchronize()
+    assert lib.dd_photo_loss_part(C.byref(args), L.current_stream(), 3) != 0
+    torch.cuda.synchronize()
+    assert torch.equal(sums, t["sums"])
+    for a, b in zip(ref, grads_of(t)):
+        assert torch.equal(a, b)
