@@ -175,6 +175,9 @@ SIGNATURES = {
     "dd_lidar_pose_points_workspace_bytes": (_z, [_i, _ll]),
     "dd_lidar_pose_points": (_i, [_v, _ll, C.POINTER(C.c_int32), _i, _v, _v, _v, _v, _z, _v]),
     "dd_box_fit": (_i, [_v, _i, _v, _v, _i, _v, _v, _i, _v, _v, _v]),
+    "dd_range_image_points_workspace_bytes": (_z, [_i, _ll]),
+    "dd_range_image_points": (_i, [_v, _v, _v, _v, _ll, _ll, _ll, C.POINTER(C.c_int32), _i, _v, _v, _v, _v, _v, _v, _z, _v]),
+    "dd_undistort": (_i, [_v, _i, _i, _i, C.POINTER(_d), _v, _v]),
     "dd_resize_area": (_i, [_v, _i, _i, _i, _v, _i, _i, _v, _v, _v, _i, _v, _v, _v, _i, _v]),
     "dd_vis_frame": (_i, [_v, _v, _v, _v, _v, _v, _v, _v, _f, _f, _i, _i, C.POINTER(C.c_int), _i, _i, _i, _v, _f, _f, _f, _f, _i, _i, _v, _v, _v, _v]),
     "dd_vis_flow_tiles": (_i, [_v, _v, C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i, _f, _i, _v, _v]),

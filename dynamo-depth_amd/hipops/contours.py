@@ -129,3 +129,87 @@ def fill_contours(vertices, contours, H, W, out=None):
     L.check(L.load().dd_fill_contours(abi.ptr(vertices), int(vertices.shape[1]), abi.ptr(contours), int(contours.shape[1]), B, H, W, abi.ptr(out),
                                       L.current_stream()), "dd_fill_contours")
     return out
+
+
+_CODE_DX = (1, 1, 0, -1, -1, -1, 0, 1)
+_CODE_DY = (0, -1, -1, -1, 0, 1, 1, 1)
+_NBD, _RIGHT = 2, -126              # the marks of a followed border pixel; _RIGHT where the border leaves it to the right
+
+
+def _follow(buf, start, step, x, y, is_hole):
+    """One border of Suzuki and Abe's algorithm from buf[start] = pixel (x, y), 8-connected, marked as it goes: its vertices, those
+    where the direction changes, in the order it is walked."""
+    deltas = tuple(dx + dy * step for dx, dy in zip(_CODE_DX, _CODE_DY)) * 2
+    out = []
+    s_end = s = 0 if is_hole else 4
+    while True:                                                 # the first neighbour, clockwise from the side the scan came from
+        s = (s - 1) & 7
+        i1 = start + deltas[s]
+        if buf[i1] != 0 or s == s_end:
+            break
+    if s == s_end:                                              # an isolated pixel
+        buf[start] = _RIGHT
+        out.append((x, y))
+        return out
+    i3, prev_s = start, s ^ 4
+    while True:
+        s_end = s
+        while True:                                             # counter-clockwise to the next border pixel
+            s += 1
+            i4 = i3 + deltas[s]
+            if buf[i4] != 0:
+                break
+        s &= 7
+        if s - 1 < s_end and s >= 1:                            # unsigned(s - 1) < unsigned(s_end): the pixel to the right was passed over
+            buf[i3] = _RIGHT
+        elif buf[i3] == 1:
+            buf[i3] = _NBD
+        if s != prev_s:
+            out.append((x, y))
+            prev_s = s
+        x, y = x + _CODE_DX[s], y + _CODE_DY[s]
+        if i4 == start and i3 == i1:
+            return out
+        i3 = i4
+        s = (s + 4) & 7
+
+
+def trace(mask):
+    """`cv2.findContours(mask, cv2.RETR_TREE, cv2.CHAIN_APPROX_SIMPLE)[0]` without cv2: the outer and the hole borders of the
+    8-connected non-zero pixels of a (H, W) or (H, W, 1) mask by Suzuki and Abe's border following, as a list of (n, 1, 2) int32
+    arrays of [x, y] vertices, kept only where the direction changes.  An outer border starts at its first pixel in raster order
+    and runs counter-clockwise on the screen (y down), a hole border at the foreground pixel left of the hole's first pixel, and
+    runs clockwise.  The contours come in the order the raster scan meets them (cv2 lists the same contours in another order;
+    `fill_host` and dd_fill_contours are even-odd over all of them).  Only the bounding box of the non-zero pixels, with one pixel
+    of margin, is visited."""
+    m = np.asarray(mask)
+    if m.ndim == 3 and m.shape[2] == 1:
+        m = m[:, :, 0]
+    if m.ndim != 2:
+        raise ValueError("trace takes a (H, W) or (H, W, 1) mask")
+    fg = m != 0
+    rows, cols = np.flatnonzero(fg.any(axis=1)), np.flatnonzero(fg.any(axis=0))
+    if rows.size == 0:
+        return []
+    ya, xa = int(rows[0]), int(cols[0])
+    box = fg[ya:int(rows[-1]) + 1, xa:int(cols[-1]) + 1]
+    h, w = box.shape
+    step = w + 2
+    img = np.zeros((h + 2, step), dtype=np.int8)
+    img[1:-1, 1:-1] = box
+    buf = img.reshape(-1).tolist()
+    found = []
+    for y in range(1, h + 1):
+        base, prev = y * step, 0
+        for x in range(1, step):
+            p = buf[base + x]
+            if p == prev:
+                continue
+            if prev == 0 and p == 1:
+                found.append(_follow(buf, base + x, step, x, y, False))
+                p = buf[base + x]                               # the scan goes on from the mark it has just been given
+            elif p == 0 and prev >= 1:
+                found.append(_follow(buf, base + x - 1, step, x - 1, y, True))
+            prev = p
+    off = np.array([xa - 1, ya - 1], dtype=np.int32)
+    return [(np.array(c, dtype=np.int32) + off).reshape(-1, 1, 2) for c in found]

@@ -21,7 +21,8 @@ ignored), one matrix `P` (float64 3x4) and an image H x W with W >= 2:
 
 Below the KITTI part: the nuScenes preparation's pose chain (`pose_points_host`, `pose_points`; csrc/dd_lidar.hip dd_lidar_pose_points) and
 the key frames' box fit (`box_fit_host`, `box_fit`, `motion_labels`; dd_box_fit), DESIGN 4.22, with pyquaternion's rotation matrix and the
-devkit's box corners written out."""
+devkit's box corners written out.  Last the Waymo preparation's range images (`range_image_points_host`, `range_image_points`;
+csrc/dd_range_image.hip) and upright box corners, DESIGN 4.23."""
 import ctypes
 import os
 
@@ -343,3 +344,162 @@ def split_rows(rows, counts, offsets):
         n = int(off[s + 1] - off[s])
         out.append([host[C * off[s] + c * n:C * off[s] + c * n + int(cnt[s, c])].copy() for c in range(C)])
     return out
+
+
+RI_STRIDE = 64          # doubles per image of dd_range_image_points' params
+AXIS_SWAP = np.array([[0, 0, 1, 0], [-1, 0, 0, 0], [0, -1, 0, 0], [0, 0, 0, 1]], dtype=np.float64)     # (x front, y left, z up) -> (x right, y down, z front)
+
+
+def inclination_table(height, beam_inclinations, inclination_min, inclination_max):
+    """float64 (height,) inclination of every row of a range image: the calibration's list where it has one, else uniform between the
+    two bounds, (0.5 + i) / height * (max - min) + min; reversed, so that row 0 looks up."""
+    height = int(height)
+    if len(beam_inclinations):
+        table = np.asarray(beam_inclinations, dtype=np.float64).reshape(-1)
+        if table.size != height:
+            raise ValueError("{} beam inclinations for a range image of {} rows".format(table.size, height))
+    else:
+        table = (0.5 + np.arange(height, dtype=np.float64)) / height * (float(inclination_max) - float(inclination_min)) + float(inclination_min)
+    return np.ascontiguousarray(table[::-1])
+
+
+def range_image_trig(inclinations, width, extrinsic):
+    """float64 (2 H + 2 W,): cos incl, sin incl per row, then cos az, sin az per column with
+    az = ((W - c - 0.5) / W * 2 - 1) * pi - atan2(E[1][0], E[0][0]).  The host and the device both read these values."""
+    incl = np.asarray(inclinations, dtype=np.float64).reshape(-1)
+    E = np.asarray(extrinsic, dtype=np.float64).reshape(4, 4)
+    W = int(width)
+    az = ((W - np.arange(W, dtype=np.float64) - 0.5) / W * 2.0 - 1.0) * np.pi - np.arctan2(E[1, 0], E[0, 0])
+    return np.concatenate([np.cos(incl), np.sin(incl), np.cos(az), np.sin(az)])
+
+
+def vehicle_to_camera(cam_extrinsic):
+    """inv(extrinsic @ axis_swap) of reference waymo.py:216-220, float64 (4, 4)."""
+    return np.linalg.inv(np.asarray(cam_extrinsic, dtype=np.float64).reshape(4, 4) @ AXIS_SWAP)
+
+
+def range_image_params(extrinsic, frame_pose, e2c, K, width, height):
+    """The RI_STRIDE doubles of one image: the laser's extrinsic, the inverse of the frame pose (inverted here in float64; None for
+    an image without a per-pixel pose), the vehicle-to-camera matrix, the 3x3 intrinsics and the image size."""
+    out = np.zeros(RI_STRIDE, dtype=np.float64)
+    E = np.asarray(extrinsic, dtype=np.float64).reshape(4, 4)
+    out[0:9], out[9:12] = E[:3, :3].reshape(-1), E[:3, 3]
+    F = np.eye(4) if frame_pose is None else np.linalg.inv(np.asarray(frame_pose, dtype=np.float64).reshape(4, 4))
+    out[13:22], out[22:25] = F[:3, :3].reshape(-1), F[:3, 3]
+    C = np.asarray(e2c, dtype=np.float64).reshape(4, 4)
+    out[25:34], out[34:37] = C[:3, :3].reshape(-1), C[:3, 3]
+    out[37:46] = np.asarray(K, dtype=np.float64).reshape(-1)
+    out[46], out[47] = width, height
+    return out
+
+
+def range_image_points_host(ranges, cps, poses, trigs, params):
+    """The definition of dd_range_image_points.  Per image s: ranges[s] (H, W) float32, cps[s] (H, W, >= 3) int32, poses[s] (H, W, 6)
+    float32 (roll, pitch, yaw, x, y, z) or None, trigs[s] from `range_image_trig`, params[s] from `range_image_params` -> a list of
+    (points float64 (n, 3), cp int32 (n, 3), rows float64 (m, 3) [u, v, depth]) and counts int32 (S, 2): the valid pixels (range > 0)
+    and of those the ones the camera keeps, both in row-major order.  float64, every dot product summed left to right; the
+    library's float32 point is not reproduced."""
+    out, counts = [], np.zeros((len(ranges), 2), dtype=np.int32)
+    for s, (rng, cp, pose, trig) in enumerate(zip(ranges, cps, poses, trigs)):
+        q = np.asarray(params[s], dtype=np.float64).reshape(RI_STRIDE)
+        rng = np.asarray(rng, dtype=np.float32)
+        H, W = rng.shape
+        t = np.asarray(trig, dtype=np.float64).reshape(2 * H + 2 * W)
+        ci, si, ca, sa = t[:H, None], t[H:2 * H, None], t[None, 2 * H:2 * H + W], t[None, 2 * H + W:]
+        rho = rng.astype(np.float64)
+        with np.errstate(all="ignore"):
+            p = [(ca * ci) * rho, (sa * ci) * rho, si * rho]
+            p = [c + k for c, k in zip(_rotate(q[0:9], p), q[9:12])]
+            if pose is not None:
+                e = [np.asarray(pose, dtype=np.float32)[:, :, k].astype(np.float64) for k in range(6)]
+                cr, sr, cq, sq, cy, sy = np.cos(e[0]), np.sin(e[0]), np.cos(e[1]), np.sin(e[1]), np.cos(e[2]), np.sin(e[2])
+                R = [cy * cq, (cy * sq) * sr - sy * cr, (cy * sq) * cr + sy * sr,
+                     sy * cq, (sy * sq) * sr + cy * cr, (sy * sq) * cr - cy * sr,
+                     -sq, cq * sr, cq * cr]
+                p = [(R[3 * k] * p[0] + R[3 * k + 1] * p[1]) + R[3 * k + 2] * p[2] + e[3 + k] for k in range(3)]
+                p = [c + k for c, k in zip(_rotate(q[13:22], p), q[22:25])]
+            valid = rng > 0
+            c = [c + k for c, k in zip(_rotate(q[25:34], p), q[34:37])]
+            a = _rotate(q[37:46], c)
+            u, v = a[0] / a[2], a[1] / a[2]
+            keep = valid & (a[2] > 0) & (u >= 0) & (u < q[46]) & (v >= 0) & (v < q[47])
+        points = np.stack([c[valid] for c in p], axis=1)
+        rows = np.stack([u[keep], v[keep], a[2][keep]], axis=1)
+        out.append((points, np.ascontiguousarray(np.asarray(cp)[:, :, :3][valid], dtype=np.int32), rows))
+        counts[s] = (points.shape[0], rows.shape[0])
+    return out, counts
+
+
+def range_image_pack(ranges, cps, poses, trigs):
+    """The flat host arrays of one dd_range_image_points call: (range float32 [n], cp int32 (n, 3), pose float32 (n_pose, 6), trig
+    float64 [n_trig], desc int32 (S, 5))."""
+    desc = np.zeros((len(ranges), 5), dtype=np.int32)
+    pix = n_pose = n_trig = 0
+    for s, (rng, pose, trig) in enumerate(zip(ranges, poses, trigs)):
+        H, W = np.shape(rng)
+        desc[s] = (pix, H, W, n_pose if pose is not None else -1, n_trig)
+        pix, n_trig = pix + H * W, n_trig + len(trig)
+        n_pose += H * W if pose is not None else 0
+    flat_pose = [np.asarray(p, dtype=np.float32).reshape(-1, 6) for p in poses if p is not None]
+    return (np.concatenate([np.asarray(r, dtype=np.float32).reshape(-1) for r in ranges]),
+            np.concatenate([np.asarray(c)[:, :, :3].reshape(-1, 3) for c in cps]).astype(np.int32, copy=False),
+            np.concatenate(flat_pose) if flat_pose else np.zeros((0, 6), dtype=np.float32),
+            np.concatenate([np.asarray(t, dtype=np.float64).reshape(-1) for t in trigs]), desc)
+
+
+def range_image_points_device(rng, cp, pose, trig, desc, params):
+    """One dd_range_image_points call on the current stream, no host sync: rng [n] float32, cp (n, 3) int32, pose (n_pose, 6) float32,
+    trig [n_trig] float64 and params (S, RI_STRIDE) float64 on the GPU, desc (S, 5) int32 on the host (`range_image_pack`) ->
+    (points (n, 3) float64, cp_out (n, 3) int32, rows (n, 3) float64, counts (S, 2) int32) on the GPU, image s in the rows from
+    desc[s, 0] on."""
+    import torch
+
+    from . import abi
+    from . import lib as L
+    ok = (torch.is_tensor(t) and t.is_cuda and t.dtype == d and t.dim() == n for t, d, n in
+          ((rng, torch.float32, 1), (cp, torch.int32, 2), (pose, torch.float32, 2), (trig, torch.float64, 1), (params, torch.float64, 2)))
+    if not all(ok) or cp.shape[1] != 3 or pose.shape[1] != 6 or params.shape[1] != RI_STRIDE or cp.shape[0] != rng.shape[0]:
+        raise L.DynamoHipError("range_image_points takes float32 ranges, (n, 3) int32 projections, (n_pose, 6) float32 poses, float64 tables and "
+                               "(S, {}) float64 parameters on the GPU".format(RI_STRIDE))
+    desc = np.ascontiguousarray(np.asarray(desc, dtype=np.int32).reshape(-1, 5))
+    S, n = desc.shape[0], int(rng.shape[0])
+    if S < 1 or S != int(params.shape[0]) or n < 1:
+        raise L.DynamoHipError("range_image_points: one descriptor and one parameter row per image, at least one pixel")
+    lib = L.load()
+    rng, cp, pose, trig, params = (t.contiguous() for t in (rng, cp, pose, trig, params))
+    dev = rng.device
+    points = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    cp_out = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    rows = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    counts = torch.empty((S, 2), dtype=torch.int32, device=dev)
+    need = int(lib.dd_range_image_points_workspace_bytes(S, int((desc[:, 1].astype(np.int64) * desc[:, 2]).max())))
+    work = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+    L.check(lib.dd_range_image_points(abi.ptr(rng), abi.ptr(cp), abi.ptr(pose) if pose.shape[0] else None, abi.ptr(trig), n, int(pose.shape[0]),
+                                      int(trig.shape[0]), desc.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), S, abi.ptr(params), abi.ptr(counts),
+                                      abi.ptr(points), abi.ptr(cp_out), abi.ptr(rows), abi.ptr(work), need, L.current_stream()),
+            "dd_range_image_points")
+    return points, cp_out, rows, counts
+
+
+def range_image_points(ranges, cps, poses, trigs, params):
+    """`range_image_points_host` on the device from host arrays, one call for all the images: the same (list, counts)."""
+    import torch
+    rng, cp, pose, trig, desc = range_image_pack(ranges, cps, poses, trigs)
+    up = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (rng, cp, pose, trig, np.asarray(params, dtype=np.float64).reshape(-1, RI_STRIDE))]
+    points, cp_out, rows, counts = (t.cpu().numpy() for t in range_image_points_device(up[0], up[1], up[2], up[3], desc, up[4]))
+    out = []
+    for s in range(desc.shape[0]):
+        a, n, m = int(desc[s, 0]), int(counts[s, 0]), int(counts[s, 1])
+        out.append((points[a:a + n].copy(), cp_out[a:a + n].copy(), rows[a:a + m].copy()))
+    return out, counts
+
+
+def upright_box_corners(box):
+    """float64 (8, 3): the Waymo library's get_upright_3d_box_corners for [center_x, center_y, center_z, length, width, height,
+    heading]: corner 0 at (+l/2, +w/2, -h/2), corners 1, 3 and 4 across the length, the width and the height from it, rotated by the
+    heading about z and moved to the centre."""
+    cx, cy, cz, l, w, h, heading = (float(v) for v in box)
+    c, s = np.cos(heading), np.sin(heading)
+    R = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]])
+    local = 0.5 * np.array([[l, w, -h], [-l, w, -h], [-l, -w, -h], [l, -w, -h], [l, w, h], [-l, w, h], [-l, -w, h], [l, -w, h]], dtype=np.float64)
+    return local @ R.T + np.array([cx, cy, cz])

@@ -18,7 +18,6 @@ exist are kept, as in the reference; an existing depth list is compared with the
 threads reads and writes files, the main thread launches.  `prepare` takes the device steps as callables, so the walk can be driven
 on the host (tests/test_nuscenes_prepare.py)."""
 import argparse
-import io
 import json
 import os
 import os.path as osp
@@ -30,71 +29,16 @@ if proj_dir not in sys.path:
     sys.path.insert(0, proj_dir)
 
 import numpy as np  # noqa: E402
-from PIL import Image  # noqa: E402
 
 from hipops import lidar  # noqa: E402
 from prepare_data import nuscenes_tables as nt  # noqa: E402
+from prepare_data.common import (JPEG_QUALITY, MAX_THREADS, chunks, device_decode, device_resize, host_decode, host_resize,  # noqa: E402,F401
+                                 pil_decode, read_bytes, save_jpeg)
 
 CAM_CHANNEL, LIDAR_CHANNEL = "CAM_FRONT", "LIDAR_TOP"
 CAM_NAME = CAM_CHANNEL[4:]
 DOWNSAMPLE_FACTOR = 3.125
-JPEG_QUALITY = 95               # cv2.imwrite's default
 EGO_CATEGORY = 31               # vehicle.ego: the camera is mounted on it
-MAX_THREADS = 16
-
-
-def pil_decode(data):
-    with Image.open(io.BytesIO(data)) as img:
-        return np.asarray(img.convert("RGB"))
-
-
-def host_decode(datas):
-    """JPEG files' bytes -> (H, W, 3) uint8 frames, by Pillow."""
-    return [pil_decode(d) for d in datas]
-
-
-def device_decode(datas):
-    """The same on the device for the files hipops.jpeg's geometry check accepts (frames stay on the GPU), by Pillow for the rest."""
-    import ctypes as C
-
-    import torch
-
-    from hipops import jpeg
-    from hipops import lib as L
-    lib = L.load()
-    out, groups = [None] * len(datas), {}
-    for n, data in enumerate(datas):
-        try:
-            rec, (w, h, ncomp, hs, vs) = jpeg.parse_header(data)
-        except jpeg.UnsupportedJpeg:
-            rec = None
-        if rec is None or ncomp != 3 or not lib.dd_jpeg_workspace_bytes(1, h, w, ncomp, (C.c_int * 3)(*hs), (C.c_int * 3)(*vs)):
-            out[n] = pil_decode(data)
-        else:
-            groups.setdefault((h, w, ncomp, hs, vs), []).append((n, rec))
-    for geom, members in groups.items():
-        cap = (max(len(datas[n]) for n, _ in members) + 4095) // 4096 * 4096
-        buf = np.zeros((len(members), cap), dtype=np.uint8)
-        for k, (n, _) in enumerate(members):
-            buf[k, :len(datas[n])] = np.frombuffer(datas[n], dtype=np.uint8)
-        frames = jpeg.decode_batch(torch.from_numpy(buf).cuda(), torch.from_numpy(np.stack([rec for _, rec in members])).cuda(), *geom)
-        for k, (n, _) in enumerate(members):
-            out[n] = frames[k]
-    return out
-
-
-def host_resize(frames, height, width):
-    from hipops import resize
-    return resize.resize_area_host(np.stack(frames), height, width)
-
-
-def device_resize(frames, height, width):
-    """Equal-sized frames (GPU tensors or host arrays) -> (n, height, width, 3) uint8 on the host, one launch."""
-    import torch
-
-    from hipops import resize
-    stack = torch.stack([f if torch.is_tensor(f) else torch.from_numpy(np.ascontiguousarray(f)).cuda() for f in frames])
-    return resize.resize_area_batch(stack, height, width).cpu().numpy()
 
 
 def host_pose_rows(scans, params):
@@ -114,19 +58,6 @@ def device_pose_rows(scans, params):
 def link(src, dst):
     if not osp.lexists(dst):
         os.symlink(osp.realpath(src), dst)
-
-
-def read_bytes(path):
-    with open(path, "rb") as fh:
-        return fh.read()
-
-
-def save_jpeg(job):
-    Image.fromarray(job[1]).save(job[0], quality=JPEG_QUALITY)
-
-
-def chunks(items, size):
-    return [items[i:i + size] for i in range(0, len(items), size)]
 
 
 def associate(nusc, sc):

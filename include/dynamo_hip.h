@@ -506,6 +506,37 @@ int dd_lidar_pose_points(const float* points, long long n_total, const int32_t* 
 int dd_box_fit(const double* points, int n_points, const int32_t* seg, const int32_t* label_cat, int L, const double* boxes,
                const int32_t* box_cat, int B, int32_t* counts, int32_t* best, void* stream);
 
+/* Waymo range images to vehicle-frame points and one camera's depth list (reference prepare_data/waymo.py:183-186, 213-241);
+ * DESIGN 4.23, hipops/lidar.py range_image_points_host restates it in numpy.  S images, image s of H_s x W_s pixels.
+ * range [n_total] float32 (first return, channel 0) and cp (n_total,3) int32 (the first camera projection [camera, x, y]), image s
+ *   from pixel desc[s][0] on, row-major.  pose (n_pose,6) float32 (roll, pitch, yaw, x, y, z) for the images that carry a per-pixel
+ *   pose, NULL when n_pose is 0.  trig [n_trig] float64, per image cos incl [H], sin incl [H], cos az [W], sin az [W], built on the host.
+ * desc (S,5) int32 on the HOST: first pixel, H, W, first pose pixel or -1, first trig word; the images' pixel ranges ascend and do
+ *   not overlap.
+ * params (S,64) float64 on the device, per image: E_R[9] E_t[3], one unused word, F_R[9] F_t[3] (inverse frame pose, used with a
+ *   pose), C_R[9] C_t[3] (vehicle to camera), K[9], width, height, 16 unused words; row-major, p' = R p + t.
+ *   p = rho (cos az cos incl, sin az cos incl, sin incl); p = E p; with a pose p = Rz(yaw) Ry(pitch) Rx(roll) p + (x, y, z), p = F p;
+ *   valid where rho > 0.  a = K (C p); kept where a_z > 0, 0 <= a_x/a_z < width, 0 <= a_y/a_z < height.  float64, unfused.
+ * counts (S,2) int32 [valid, kept].  points (n_total,3) float64, cp_out (n_total,3) int32: image s writes its valid pixels in
+ *   row-major order from row desc[s][0]; rows (n_total,3) float64 [a_x/a_z, a_y/a_z, a_z] of its kept pixels likewise; the rest of
+ *   a segment is left as it was.
+ * workspace: dd_range_image_points_workspace_bytes(S, largest H*W), 4-byte aligned.  5 launches per 16 images, no atomics.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer, a non-positive size, a descriptor that leaves its array or overlaps
+ * the one before, a workspace that is too small, a misaligned pointer. */
+size_t dd_range_image_points_workspace_bytes(int S, long long hw_max);
+int dd_range_image_points(const float* range, const int32_t* cp, const float* pose, const double* trig, long long n_total, long long n_pose,
+                          long long n_trig, const int32_t* desc, int S, const double* params, int32_t* counts, double* points,
+                          int32_t* cp_out, double* rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Lens undistortion, cv2.undistort(img, K, dist) with the new camera matrix equal to K (reference prepare_data/waymo.py:10-27):
+ * src (n,H,W,3) uint8 -> dst (n,H,W,3) uint8, both 4-byte aligned, frames that share one calibration.  intrinsic [9] float64 on the
+ * HOST: f_u, f_v, c_u, c_v, k1, k2, p1, p2, k3.  The source position of every destination pixel in float64 (unfused, in the order
+ * csrc/dd_undistort.hip fixes), rounded half to even to 1/32 pixel; bilinear in integers with the weights (32-a)(32-b), a(32-b),
+ * (32-a)b, ab, taps outside the image 0, (sum + 512) >> 10; DESIGN 4.23, hipops/undistort.py undistort_host.  One launch.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer, a non-positive size, H*W*3 above 2^31-1, a NaN in the intrinsic or a
+ * focal length of 0, a misaligned pointer. */
+int dd_undistort(const unsigned char* src, int n, int H, int W, const double* intrinsic, unsigned char* dst, void* stream);
+
 /* Training-mode nn.BatchNorm2d on a channels-last tensor, with the activation that follows it and an optional residual add
  * fused into the normalisation pass: out = act(bn(x) [+ residual]).  Covers torchvision BasicBlock's bn1->relu and
  * bn2(+identity)->relu as used by networks/resnet_encoder.py:42-88, the stem bn1->relu, and LiteMono's BNGELU / DilatedConv.bn1
