@@ -12,6 +12,8 @@ DD_MODE_RIGID, DD_MODE_FLOW, DD_MODE_FLOW_MASK = 0, 1, 2
 DD_PARTIAL_STRIDE = 40
 DD_SUMS_STRIDE = 8
 DD_OBJECTS_ROW = 22         # 32-bit words per row of dd_objects' table
+DD_TRACKS_LINK = 6          # 32-bit words per row of dd_tracks_link's links
+DD_TRACKS_MAX_OBJECTS = 1024
 DD_DTYPE_F32, DD_DTYPE_F16, DD_DTYPE_BF16 = 0, 1, 2         # `dtype` of the element-typed (_t) entry points
 
 _fp = C.c_void_p        # device (or, for the host-math test library, host) float*
@@ -188,6 +190,7 @@ SIGNATURES = {
     "dd_objects_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dd_objects": (_i, [_v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _i, _i, _i, _v, _v, _v, _v, _z, _v]),
     "dd_export_labels_u16": (_i, [_v, _i, _i, _i, _i, _i, _v, _v]),
+    "dd_tracks_link": (_i, [_v, _v, _v, _v, _v, _v, _v, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _v, _v, _v]),
     "dd_bn_workspace_bytes": (_z, [_i]),
     "dd_bn_act_fwd_t": (_i, [_v, _v, _ll, _i, _v, _v, _f, _f, _v, _v, _v, _v, _i, _v, _i, _v, _z, _v]),
     "dd_bn_act_bwd_t": (_i, [_v, _v, _v, _ll, _i, _v, _v, _v, _v, _i, _v, _v, _v, _v, _i, _v, _z, _v]),

@@ -1,10 +1,10 @@
 """Depth for a folder of frames, at the frames' own resolution:
 
     python predict.py <frames dir> -l <checkpoint folder> [--depth_model ...] [--height H --width W] [-b B] [--out <dir>]
-                      [--save depth16 npy color cloud objects] [--depth_scale 256] [--post_process] [--motion] [--scene]
+                      [--save depth16 npy color cloud objects tracks] [--depth_scale 256] [--post_process] [--motion] [--scene]
                       [--intrinsics fx fy cx cy] [--cloud_stride 1] [--cloud_max_range R] [--cloud_edge 0.05] [--cloud_motion_thresh 0.5]
                       [--object_motion_thresh 0.5] [--object_connectivity 8] [--object_min_pixels 16] [--object_max 256]
-                      [--write_threads 8]
+                      [--track_min_iou 0.25] [--write_threads 8]
 
 The counterpart of the reference's quick demo on a few frames (its README's first offer; the demo notebook goes through
 eval/visualize.py get_vis and shows the network-resolution disparity): no dataset layout, no split list.  The frames are read by
@@ -17,6 +17,8 @@ Per frame, named by the source file's stem:
     <out>/cloud/<stem>.ply        the frame as a coloured point cloud in its own camera coordinates (binary PLY)   (--save cloud)
     <out>/objects/<stem>.png      16-bit label image of the moving objects at the source size, 0 = none       (--motion --save objects)
     <out>/objects/<stem>.json     the frame's objects: id, pixels, box, centroid, motion, speed, confidence, z_min, z_max
+    <out>/tracks/<stem>.png       the label image of the objects with every object number replaced by its track id (--motion --save tracks)
+    <out>/tracks.json             per track its id, first and last frame, length, path length and its object in every frame
     <out>/predict.json            min_depth, max_depth, depth_scale, the network resolution; depth is up to scale
 depth = 1 / bilinear(disp_to_depth(disp)) at the source size: the depth metrics' definition of a prediction (tools.py:42, 291-298),
 written by one kernel per batch (hipops.export, csrc/dd_export.hip); only the bytes that go to disk cross to the host.
@@ -34,6 +36,11 @@ scene of the drive, the moving objects removed by the network's own mask.  Depth
 order of their first pixel, at most --object_max per frame.  Per object its size, its box in source pixels, the mean of its points in
 the frame's camera coordinates (centroid), its own mean 3-D motion to the neighbouring frame with the ego-motion removed (motion,
 speed), its mean mask value (confidence) and its depth range: hipops.objects, csrc/dd_objects.hip, labelled and reduced on the device.
+--save tracks (with --motion, frames of one size, frame_ids[1] == -1) gives the same object one identity through the drive: every pixel
+of an object of frame i is carried by the network's own complete flow into the camera of frame i-1 and votes for the object it lands
+on there (hipops.tracks, csrc/dd_tracks.hip, on the device); an object continues the track of the predecessor's object it shares most
+pixels with when their intersection over union reaches --track_min_iou, otherwise it opens a new track.  A track's positions are its
+centroids in the coordinates of the first interior frame, through the pose chain of --scene.  No re-identification after a gap.
 """
 import contextlib
 import json
@@ -59,6 +66,7 @@ from Trainer import Trainer  # noqa: E402
 MAX_THREADS = 16
 CLOUD = "cloud"         # --save cloud: not an output of export_depth
 OBJECTS = "objects"     # --save objects: neither
+TRACKS = "tracks"       # --save tracks: neither
 SAVE = {"depth16": ("depth16", "depth", ".png"), "npy": ("depth", "depth_npy", ".npy"), "color": ("rgb", "color", ".png")}   # --save name -> (export output, folder, extension)
 SCALE_NOTE = "depth is up to scale: a self-supervised monocular network predicts it up to one unknown factor per model"
 
@@ -68,7 +76,7 @@ def parse(argv=None):
     p = options.p
     p.add_argument("frames_dir", type=str, help="a directory of .jpg / .jpeg / .png frames")
     p.add_argument("--out", type=str, default=None, help="output directory (default: <eval_dir>/predict/<frames dir's name>)")
-    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE) + [CLOUD, OBJECTS], help="what to write per frame")
+    p.add_argument("--save", nargs="+", type=str, default=["depth16"], choices=sorted(SAVE) + [CLOUD, OBJECTS, TRACKS], help="what to write per frame")
     p.add_argument("--depth_scale", type=float, default=256.0, help="the 16-bit image holds depth * depth_scale")
     p.add_argument("--post_process", action="store_true", help="fuse the disparities of the image and of its mirror image")
     p.add_argument("--motion", action="store_true", help="triplets of frames: also the motion mask and the pose of every interior frame")
@@ -83,8 +91,15 @@ def parse(argv=None):
     p.add_argument("--object_connectivity", type=int, default=8, choices=[4, 8], help="--save objects: the neighbourhood that connects foreground pixels")
     p.add_argument("--object_min_pixels", type=int, default=16, help="--save objects: smaller components (network pixels) are not objects")
     p.add_argument("--object_max", type=int, default=256, help="--save objects: at most this many objects per frame (up to 65535)")
+    p.add_argument("--track_min_iou", type=float, default=0.25, help="--save tracks: an object continues a track when its link's intersection over union is at least this")
     opt = options.parse(args=argv)
     opt.print_opt = False
+    if TRACKS in opt.save and not opt.motion:
+        p.error("--save tracks needs --motion: the tracks link the objects of the motion mask through the motion networks' flow")
+    if TRACKS in opt.save and (len(opt.frame_ids) < 2 or opt.frame_ids[1] != -1):
+        p.error("--save tracks needs frame_ids[1] == -1: the flow has to point at the frame in front")
+    if TRACKS in opt.save and opt.object_max > 1024:
+        p.error("--save tracks takes an --object_max of at most 1024")
     if OBJECTS in opt.save and not opt.motion:
         p.error("--save objects needs --motion: the objects are the components of the motion mask, their motion comes from the motion networks")
     if opt.object_min_pixels < 1 or not 1 <= opt.object_max <= 65535:
@@ -184,13 +199,31 @@ def object_parameters(opt):
             "min_pixels": int(getattr(opt, "object_min_pixels", 16)), "max_objects": int(getattr(opt, "object_max", 256))}
 
 
-def export_objects(opt, res, H, W, intrinsics, params):
-    """The batch's objects on the device: (label images (B,H,W) uint16, table, counts).  `intrinsics`: in pixels of the network's frame."""
+def track_parameters(opt):
+    """The tracks' parameter from the options: what predict.json and tracks.json record."""
+    return {"min_iou": float(getattr(opt, "track_min_iou", 0.25))}
+
+
+def export_objects(opt, res, H, W, intrinsics, params, with_labels=False):
+    """The batch's objects on the device: (label images (B,H,W) uint16, table, counts), with_labels: and the labels (B,h,w) int32 at the
+    network's resolution.  `intrinsics`: in pixels of the network's frame."""
     from hipops.objects import find_objects, labels_u16
     labels, table, counts = find_objects(res["motion_mask"], res["disp"], res["complete_flow"].float(), res["ts"], res["cam_T_cam"].float(), intrinsics,
                                          disp_flipped=res.get("disp_flipped"), min_depth=opt.min_depth, max_depth=opt.max_depth, thresh=params["motion_thresh"],
                                          connectivity=params["connectivity"], min_pixels=params["min_pixels"], max_objects=params["max_objects"])
-    return labels_u16(labels, H, W), table, counts
+    return (labels_u16(labels, H, W), table, counts) + ((labels,) if with_labels else ())
+
+
+def link_batch(opt, res, labels, carry, intrinsics, params):
+    """The links of the batch's frames to their predecessors on the device: links (B, M, 6) int32.  `labels`: the batch's object labels;
+    `carry`: the label map of the frame in front of the batch (1,h,w), None at the drive's first interior frame, whose row links to an
+    empty map and is not used."""
+    from hipops.tracks import link_objects
+    before = torch.zeros_like(labels[:1]) if carry is None else carry
+    labels_dst = torch.cat([before, labels[:-1]], dim=0)            # the one device copy: every frame's predecessor beside it
+    _, links = link_objects(labels, labels_dst, res["disp"], res["complete_flow"].float(), res["ts"], intrinsics, disp_flipped=res.get("disp_flipped"),
+                            min_depth=opt.min_depth, max_depth=opt.max_depth, max_objects=params["max_objects"])
+    return links
 
 
 def _write_json(path, value):
@@ -222,16 +255,25 @@ def _write(path, array):
 
 
 def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_scale=256.0, post_process=False, motion=False, intrinsics=None,
-                   write_threads=8, scene=False, cloud=None, objects=None):
+                   write_threads=8, scene=False, cloud=None, objects=None, tracks=None):
     """Every frame of `frames_dir` (with motion: every interior frame) -> the files described above; returns the written paths.
     The main thread launches and makes one copy to the host per batch and requested output; a thread pool encodes and writes.
-    `cloud`: cloud_parameters(opt), for --save cloud and `scene`; `objects`: object_parameters(opt), for --save objects."""
+    `cloud`: cloud_parameters(opt), for --save cloud and `scene`; `objects`: object_parameters(opt), for --save objects
+    and --save tracks; `tracks`: track_parameters(opt), for --save tracks."""
     from hipops.cloud import RECORD, ScenePly, write_ply
     save = tuple(dict.fromkeys(save))
-    want_cloud, want_objects, save = CLOUD in save, OBJECTS in save, tuple(name for name in save if name not in (CLOUD, OBJECTS))
+    want_cloud, want_objects, want_tracks = CLOUD in save, OBJECTS in save, TRACKS in save
+    save = tuple(name for name in save if name not in (CLOUD, OBJECTS, TRACKS))
     if want_objects and not motion:
         raise ValueError("the objects need the motion networks (--motion)")
     object_params = dict(objects) if objects is not None else object_parameters(opt)
+    track_params = dict(tracks) if tracks is not None else track_parameters(opt)
+    if want_tracks and not motion:
+        raise ValueError("the tracks need the motion networks (--motion)")
+    if want_tracks and (len(opt.frame_ids) < 2 or opt.frame_ids[1] != -1):
+        raise ValueError("the tracks need frame_ids[1] == -1, not frame_ids = {}: the flow has to point at the frame in front".format(list(opt.frame_ids)))
+    if want_tracks and object_params["max_objects"] > 1024:
+        raise ValueError("the tracks take at most 1024 objects per frame, not {}".format(object_params["max_objects"]))
     if scene and not motion:
         raise ValueError("the scene cloud needs the motion networks (--motion)")
     params = dict(cloud) if cloud is not None else cloud_parameters(opt)
@@ -245,12 +287,18 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
         by_size.setdefault(whole.get_gt_dim(None, i, None), []).append(i)
     if scene and len(by_size) != 1:
         raise ValueError("--scene needs frames of one size, {} holds {}".format(frames_dir, sorted(by_size)))
-    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else []) + ([CLOUD] if want_cloud else []) + ([OBJECTS] if want_objects else [])
+    if want_tracks and len(by_size) != 1:
+        raise ValueError("--save tracks needs frames of one size, so that a batch holds consecutive frames; {} holds {}".format(frames_dir, sorted(by_size)))
+    folders = [SAVE[name][1] for name in save] + (["motion_mask"] if motion else []) + ([CLOUD] if want_cloud else []) + ([OBJECTS] if want_objects else []) + ([TRACKS] if want_tracks else [])
     ext = {SAVE[name][1]: SAVE[name][2] for name in save}
     for folder in folders:
         os.makedirs(osp.join(out_dir, folder), exist_ok=True)
     pending, poses, counts, scene_counts, used_intrinsics, object_counts = [], {}, {}, {}, {}, {}
     scene_file, chain = (ScenePly(osp.join(out_dir, "scene.ply")) if scene else None), None
+    builder, carry = None, None             # --save tracks: the tracks so far, the label map of the last frame of the batch before
+    if want_tracks:
+        from hipops.tracks import TrackBuilder, track_image, tracks_json
+        builder = TrackBuilder(track_params["min_iou"])
     with ThreadPoolExecutor(max_workers=min(max(int(write_threads), 1), MAX_THREADS)) as pool, (scene_file or contextlib.nullcontext()):
         for (H, W), idx in sorted(by_size.items()):
             dataset = folder_dataset(opt, trainer, frames_dir, idx, intrinsics)
@@ -258,7 +306,7 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                                 collate_fn=dataset.collate, **trainer._worker_start())
             for inputs in loader:
                 stems = list(inputs["paths"])
-                extra = dict(objects=True) if want_objects else {}           # only then: the call is what it was without
+                extra = dict(objects=True) if want_objects or want_tracks else {}           # only then: the call is what it was without
                 if want_cloud or scene:
                     res = predict_batch(opt, trainer, inputs, post_process=post_process, motion=motion, cloud=True, **extra)
                     camera = used_intrinsics.setdefault("{}x{}".format(H, W), cloud_intrinsics(dataset.K, H, W))
@@ -267,9 +315,10 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                 files = export_batch(opt, res, H, W, save, depth_scale)
                 clouds = export_clouds(opt, res, H, W, camera, params) if want_cloud else None
                 pose = res["cam_T_cam"].reshape(-1, 16).cpu().numpy() if motion else None
-                if scene:
+                if scene or want_tracks:
                     G = chain_poses(pose, chain)
                     chain = G[-1]
+                if scene:
                     world = torch.from_numpy(np.ascontiguousarray(G[:, :3].astype(np.float32))).to(res["disp"].device)
                     data, off = _fetch_clouds(*export_clouds(opt, res, H, W, camera, params, pose=world, static=True))
                     scene_file.append(data)
@@ -279,16 +328,30 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
                     for b, stem in enumerate(stems):
                         counts[stem] = int(off[b + 1] - off[b])
                         pending.append(pool.submit(write_ply, osp.join(out_dir, CLOUD, stem + ".ply"), data[off[b] * RECORD:off[b + 1] * RECORD]))
-                if want_objects:
+                if want_tracks:
+                    from hipops.objects import unpack_table
+                    h, w = res["disp"].shape[-2:]
+                    images, table, found, labels = export_objects(opt, res, H, W, cloud_intrinsics(dataset.K, h, w), object_params, with_labels=True)
+                    links = link_batch(opt, res, labels, carry, cloud_intrinsics(dataset.K, h, w), object_params)
+                    first, carry = carry is None, labels[-1:]
+                elif want_objects:
                     from hipops.objects import unpack_table
                     h, w = res["disp"].shape[-2:]
                     images, table, found = export_objects(opt, res, H, W, cloud_intrinsics(dataset.K, h, w), object_params)
-                    files[OBJECTS] = images                 # the label images go to the host with the other images below
+                if want_objects or want_tracks:
+                    if want_objects:
+                        files[OBJECTS] = images             # the label images go to the host with the other images below
                     packed = torch.cat([table.reshape(len(stems), -1), found], dim=1).cpu().numpy()      # the batch's one copy of the tables
                     frames = unpack_table(packed[:, :-3].reshape(tuple(table.shape)), packed[:, -3:], size=(h, w, H, W))
                     for stem, frame in zip(stems, frames):
                         object_counts[stem] = {"kept": len(frame["objects"]), "found": frame["found"], "truncated": frame["truncated"]}
-                        pending.append(pool.submit(_write_json, osp.join(out_dir, OBJECTS, stem + ".json"), frame))
+                        if want_objects:
+                            pending.append(pool.submit(_write_json, osp.join(out_dir, OBJECTS, stem + ".json"), frame))
+                if want_tracks:
+                    rows, label_images = links.cpu().numpy(), images.cpu().numpy()
+                    for b, stem in enumerate(stems):
+                        ids = builder.add(stem, frames[b]["objects"], None if first and b == 0 else rows[b], G[b])
+                        pending.append(pool.submit(_write, osp.join(out_dir, TRACKS, stem + ".png"), track_image(label_images[b], ids)))
                 for folder, tensor in files.items():
                     host = tensor.cpu().numpy()             # the batch's one copy of this output
                     for b, stem in enumerate(stems):
@@ -299,6 +362,10 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
         written = [f.result() for f in pending]
     if scene:
         written.append(scene_file.close())
+    if want_tracks:
+        from hipops.objects import MOTION_NOTE as motion_note
+        record = tracks_json(builder, dict(object_params, **track_params), notes=(SCALE_NOTE, motion_note))
+        written.append(_write_json(osp.join(out_dir, "tracks.json"), record))
     if motion:
         path = osp.join(out_dir, "poses.txt")
         with open(path, "w") as fh:
@@ -323,6 +390,8 @@ def predict_folder(opt, trainer, frames_dir, out_dir, save=("depth16",), depth_s
         meta["objects"] = dict(object_params, note=SCALE_NOTE, motion_note=MOTION_NOTE,
                                convention="x right, y down, z forward; pixel centres at integer coordinates; boxes in source pixels, inclusive",
                                frames={whole.stem(i): object_counts[whole.stem(i)] for i in indices})
+    if want_tracks:
+        meta["tracks"] = {k: record[k] for k in ("parameters", "count", "longest", "links_accepted", "links_refused", "notes")}
     with open(path, "w") as fh:
         json.dump(meta, fh, indent=2)
     written.append(path)
@@ -333,7 +402,8 @@ def main(argv=None):
     opt = parse(argv)
     trainer = build_trainer(opt)
     written = predict_folder(opt, trainer, opt.frames_dir, opt.out, save=opt.save, depth_scale=opt.depth_scale, post_process=opt.post_process,
-                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads, scene=opt.scene, cloud=cloud_parameters(opt), objects=object_parameters(opt))
+                             motion=opt.motion, intrinsics=opt.intrinsics, write_threads=opt.write_threads, scene=opt.scene, cloud=cloud_parameters(opt), objects=object_parameters(opt),
+                             tracks=track_parameters(opt))
     print("{} files written to `{}`".format(len(written), opt.out))
     return written
 

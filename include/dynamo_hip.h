@@ -917,6 +917,33 @@ int dd_objects(const float* motion_mask, const float* disp, const float* disp_fl
                size_t workspace_bytes, void* stream);
 int dd_export_labels_u16(const int* labels, int B, int h, int w, int H, int W, uint16_t* out, void* stream);
 
+/* Objects linked across frames (predict.py --save tracks; csrc/dd_tracks.hip): the vote of the network's own
+ * correspondences between two label maps.  hipops/tracks.py link_host is the definition in numpy.
+ * All maps at the network's resolution: labels_src (B,h,w) int32 the object numbers of frame i (dd_objects' labels), labels_dst (B,h,w)
+ * those of its predecessor; disp, disp_flipped, l_mask as dd_objects; complete_flow (B,3,h,w) and ts (B) of the gap to the predecessor.
+ * fx, fy, cx, cy: in pixels of the h x w image; 1/fx and 1/fy are evaluated in double and rounded to fp32 once.  lo, span: s = lo + span * d.
+ * M = max_objects.  Per pixel (y, x) of image b with a = labels_src in 1..M, fp32 and unfused: d the (fused) disparity, z = 1/(lo + span*d),
+ *   p = (xc*z, yc*z, z) with xc = ((float)x - cx)/fx, yc = ((float)y - cy)/fy;  m_k = p_k + complete_flow[b,k,y,x] * ts[b]: the point in the
+ *   predecessor's camera, no pose needed;  u = fx*(m0/m2) + cx, v = fy*(m1/m2) + cy;  uf = floorf(u + 0.5f), vf = floorf(v + 0.5f);
+ *   inside = m2 > 0 && 0 <= uf <= w-1 && 0 <= vf <= h-1, every comparison false for NaN; the conversion to int happens behind that test.
+ *   column = M+1 when not inside, else t = labels_dst[b, (int)vf, (int)uf] where t is in 1..M and 0 otherwise.
+ * A source label outside 1..M votes nowhere, a destination label outside 0..M counts as background: whatever the maps hold, no address
+ * outside the buffers is formed.
+ * votes (B, M, M+2) int32: votes[b, a-1, column] = the number of such pixels; column 0 background, 1..M objects, M+1 outside the image
+ *   or behind the camera.  Every word is written by the call.
+ * links (B, M, DD_TRACKS_LINK) int32 per row: dst, votes, dst2, votes2, background, outside.  dst: the smallest column of 1..M that holds
+ *   the row's largest count over those columns where that count is positive, else 0 with votes 0; dst2: the same over the columns other
+ *   than dst; background, outside: columns 0 and M+1.  Rows of numbers no pixel carries are zero.
+ * Three launches (memset, vote, select); no workgroup waits for another; integer atomics only: the outputs are the same bytes every run.
+ * hipErrorInvalidValue (1), nothing launched: a NULL pointer other than disp_flipped and l_mask, l_mask without disp_flipped or the
+ * reverse, B, h, w or max_objects below 1, B*h*w or B*M*(M+2) above 2^31-1, max_objects above DD_TRACKS_MAX_OBJECTS, fx or fy zero or
+ * not finite, a pointer that is not 4-byte aligned. */
+#define DD_TRACKS_LINK 6
+#define DD_TRACKS_MAX_OBJECTS 1024
+int dd_tracks_link(const int* labels_src, const int* labels_dst, const float* disp, const float* disp_flipped, const float* l_mask,
+                   const float* complete_flow, const float* ts, int B, int h, int w, float fx, float fy, float cx, float cy, float lo, float span,
+                   int max_objects, int* votes, int* links, void* stream);
+
 const char* dd_error_string(int code);
 int dd_abi_version(void);
 
